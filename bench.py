@@ -24,10 +24,14 @@ roofline      = K-sw3 (shifting-band extension, the dominant DP stage; two concu
                 execute them x 12 int32 ops per cell / HIP-event time of the stage launches, against the int32 VALU peak
 roofline_sw1  = K-sw1 (fixed-band extension between anchors, K_winalign), roofline_sw2 = K-sw2 (global banded, K_gap): same pricing
 roofline_seed = seed lookup (K_candidates): algorithmic bytes (L/4 + 16 B per probe + 4 B per seed entry) / kernel time vs 8 TB/s
-cpu_baseline  = the REAL reference `wtzmo -t 32` (oracle/_ref, prebuilt) on THE BENCH INPUT ITSELF for configs[1] / configs[2] (a same-shape sample for the larger
+cpu_baseline  = the REAL reference `wtzmo -t min(32, usable CPUs)` (oracle/_ref, prebuilt) on THE BENCH INPUT ITSELF for configs[1] / configs[2] (a same-shape sample for the larger
                 shapes), its overlap phase timed like the GPU's (from "calculating overlaps" to exit; FASTA load excluded); cpu_baseline_all_cores = the same
-                binary with -t <all hardware threads> on a bounded sample (north_star's figure: slower than -t 32, the reference's index build is O(threads x bases))
+                binary with -t <all usable CPUs> on a bounded sample (north_star's figure: slower than -t 32, the reference's index build is O(threads x bases))
 parity        = md5 of the last step's .ovl against reference `wtzmo -t 1` on the same input (tests/golden/big_manifest.json); a mismatch voids the run (exit 1)
+
+A plain run does only what the headline needs: input, warm-up, the K timed steps, --dump-outputs DIR if given (the last step's .ovl and .contained as
+.npy arrays: dump_outputs), one JSON line.  The kernel and roofline figures come from the counters of those same steps.  --full adds what takes time
+or files of its own: parity, cpu_baseline / cpu_baseline_all_cores, the PMC traffic of the newest committed profile and the build id.
 """
 from __future__ import annotations
 
@@ -119,16 +123,321 @@ def git_blob_id(path):
     return hashlib.sha1(b"blob %d\0" % len(b) + b).hexdigest()
 
 
+_PCG_MULT = 0x2360ED051FC65DA44385DF649FCCF645      # PCG64 (XSL-RR 128/64): state <- state * MULT + inc mod 2^128 before each 64-bit output
+_M128 = (1 << 128) - 1
+
+
+def usable_cpus():
+    """CPUs this process may actually run on: the affinity mask, cut by a cgroup v2 CPU quota where one is set (os.cpu_count() is the whole host's)"""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    return max(1, n)
+
+
+class _RawStream:
+    """The 64-bit outputs of one PCG64 stream, made ahead on several threads: raw(k, n) = what draws k .. k+n-1 of the generator return (draw 0 = the
+    first after seeding).  Output k only depends on the LCG state after k draws, which is a jump away.  Windows of `window` draws; the next one, which
+    starts `overlap` draws before the end of the current one, is made while the current one is read (a longer request is made on the spot).  Beside each window, one
+    flag per draw and threshold in `below`: draw < threshold (what random() < p is on the raw draw), so that the reader only counts bytes."""
+
+    def __init__(self, state, inc, threads, window, overlap, below):
+        from concurrent.futures import ThreadPoolExecutor
+        import numpy as np
+        self.np, self.s0, self.inc, self.threads, self.window, self.overlap, self.below = np, state, inc, threads, window, overlap, below
+        self.jumps = []                 # (A, C) of 2^j steps: s -> A s + C
+        a, c = _PCG_MULT, inc
+        for _ in range(128):
+            self.jumps.append((a, c))
+            a, c = (a * a) & _M128, (a * c + c) & _M128
+        self.ex = ThreadPoolExecutor(threads)
+        self.base, self.buf, self.flags, self.next = 0, np.empty(0, np.uint64), [], None
+
+    def jump(self, s, k):
+        j = 0
+        while k:
+            if k & 1:
+                a, c = self.jumps[j]
+                s = (a * s + c) & _M128
+            k >>= 1; j += 1
+        return s
+
+    def _part(self, buf, flags, k, a, b):
+        bg = self.np.random.PCG64()
+        bg.state = {"bit_generator": "PCG64", "state": {"state": self.jump(self.s0, k + a), "inc": self.inc}, "has_uint32": 0, "uinteger": 0}
+        buf[a:b] = bg.random_raw(b - a)
+        for f, T in zip(flags, self.below):
+            self.np.less(buf[a:b], T, out=f[a:b])
+
+    def _start(self, k, n):
+        np = self.np
+        buf, flags = np.empty(n, np.uint64), [np.empty(n, bool) for _ in self.below]
+        per = -(-n // self.threads)
+        return k, buf, flags, [self.ex.submit(self._part, buf, flags, k, a, min(n, a + per)) for a in range(0, n, per)]
+
+    def raw(self, k, n):
+        if k < self.base or k + n > self.base + self.buf.size:
+            nx, self.next = self.next, None
+            if nx is None or k < nx[0] or k + n > nx[0] + nx[1].size:
+                nx = self._start(k, max(n, self.window))
+            for f in nx[3]:
+                f.result()
+            self.base, self.buf, self.flags = nx[0], nx[1], nx[2]
+            self.next = self._start(self.base + self.buf.size - self.overlap, self.window)
+        return self.buf[k - self.base:k - self.base + n]
+
+    def flag(self, i, k, n):
+        """flags of threshold i over draws k .. k+n-1 (call raw(k, n) first: the window must hold them)"""
+        return self.flags[i][k - self.base:k - self.base + n]
+
+    def close(self):
+        self.ex.shutdown(wait=True, cancel_futures=True)
+
+
+def synth_fasta(path, genome_len, coverage, seed, threads=0, mean_len=10000.0, sigma=0.4, min_len=1000, err=0.15):
+    """synth.write_fasta(path, *synth.synth_reads(genome_len, coverage, seed)) with the same bytes, on several threads (a 1.2 Gbp set in seconds,
+    not a minute).  What is sequential in the generator is the order of its draws.  Here the two per-read bulk draws (random(n): one 64-bit output per
+    base) are cut out of a stream made ahead in parallel, the two small uint8 draws are decoded from the same stream exactly as numpy's bounded
+    generator does (one 32-bit word per four values, Lemire rejection), the three scalar draws per read stay numpy calls on the generator positioned
+    at the right draw, and the reads are assembled, mutated and formatted in batches on worker threads.  Returns (reads, bases, md5 of the file)."""
+    import hashlib
+    import math
+    import queue
+    import threading
+    from concurrent.futures import ThreadPoolExecutor
+    import numpy as np
+    threads = threads or min(16, usable_cpus())
+    rng = np.random.Generator(np.random.PCG64(seed))
+    bg = rng.bit_generator
+    st0 = bg.state
+    s0, inc = st0["state"]["state"], st0["state"]["inc"]
+    p_del, p_sub, p_ins = err * 0.3, err * 0.2, err * 0.5
+    # random() < p  <=>  (raw >> 11) 2^-53 < p  <=>  raw < ceil(p 2^53) << 11 (exact: the scaling is by a power of two)
+    T_del, T_ds, T_ins = (np.uint64(math.ceil(p * 9007199254740992.0) << 11) for p in (p_del, p_del + p_sub, p_ins))
+    target = int(genome_len * coverage)
+    window = min(1 << 24, 2 * target + genome_len // 8 + (1 << 20))
+    S = _RawStream(s0, inc, threads, window, min(1 << 20, window // 4), (T_del, T_ds, T_ins))
+    genome = rng.integers(0, 4, size=genome_len, dtype=np.uint8)
+    # the position of the generator: draws taken k, the buffered 32-bit half (h, w) of numpy's next_uint32; s_at = the LCG state after k_at draws
+    st = bg.state
+    words = -(-genome_len // 4)             # one 32-bit word per four values
+    k = -(-words // 2)
+    h, w = st["has_uint32"], st["uinteger"]
+    k_at, s_at = k, st["state"]["state"]
+    if S.jump(s0, k) != s_at or h != words & 1:
+        raise RuntimeError("synth_fasta: the genome draw did not take the expected %d outputs" % k)
+    checks = [64]
+    def u8(kk, hh, ww, cnt, lo):
+        """numpy's integers(lo, 4, size=cnt, dtype=uint8) at the position (kk, hh, ww): where it leaves the generator, and what build() decodes the values from"""
+        if cnt == 0:
+            return None, kk, hh, ww
+        need = cnt + 64 if lo else cnt
+        while True:
+            r = S.raw(kk, -(-need // 8) + 1)
+            if lo == 0:         # range 4: b * 4 >> 8, never rejected
+                used = cnt
+                break
+            by = r.view(np.uint8)
+            if hh:
+                by = np.concatenate([np.frombuffer(int(ww).to_bytes(4, "little"), np.uint8), by])
+            nz = np.flatnonzero(by)         # range 3: b * 3 >> 8, rejected when (3 b) mod 256 < 1, i.e. b == 0
+            if nz.size >= cnt:
+                used = int(nz[cnt - 1]) + 1
+                break
+            need *= 2
+        words = -(-used // 4) - hh
+        n64 = -(-words // 2)
+        hh2 = words & 1
+        src, ww2 = (r, hh, ww, cnt, lo), (int(r[n64 - 1]) >> 32 if hh2 else 0)
+        if checks[0]:       # the decoding restates numpy's bounded uint8 draw: numpy itself must agree on the first reads
+            checks[0] -= 1
+            bg.state = {"bit_generator": "PCG64", "state": {"state": S.jump(s0, kk), "inc": inc}, "has_uint32": hh, "uinteger": ww}
+            ref = rng.integers(lo, 4, size=cnt, dtype=np.uint8)
+            now = bg.state
+            if not (np.array_equal(ref, u8_values(src)) and now["state"]["state"] == S.jump(s0, kk + n64) and now["has_uint32"] == hh2 and (not hh2 or now["uinteger"] == ww2)):
+                raise RuntimeError("synth_fasta: numpy's integers(%d, 4, dtype=uint8) no longer draws as restated here" % lo)
+        return src, kk + n64, hh2, ww2
+
+    def u8_values(src):
+        r, hh, ww, cnt, lo = src
+        by = r.view(np.uint8)
+        if hh:
+            by = np.concatenate([np.frombuffer(int(ww).to_bytes(4, "little"), np.uint8), by])
+        if lo == 0:
+            return by[:cnt] >> 6
+        return (((by[np.flatnonzero(by)[:cnt]].astype(np.uint16) * np.uint16(3)) >> 8) + 1).astype(np.uint8)
+
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+
+    def build(first, jobs):
+        """reads first .. first+len(jobs)-1 as FASTA text: the operations of synth._mutate, over the batch at once"""
+        out = np.concatenate([genome[j[0]:j[0] + j[1]][::-1 if j[2] else 1] for j in jobs])
+        Ls = np.array([j[1] for j in jobs], np.int64)
+        beg = np.cumsum(Ls) - Ls
+        for j, b in zip(jobs, beg):
+            if j[2]:                        # reverse complement: 3 - code
+                seg = out[b:b + j[1]]
+                np.subtract(3, seg, out=seg)
+        keep = ~np.concatenate([j[3][0] for j in jobs])
+        sub = keep & np.concatenate([j[3][1] for j in jobs])
+        sv = [u8_values(j[4]) for j in jobs if j[4] is not None]
+        if sv:
+            out[sub] = (out[sub] + np.concatenate(sv)) & 3
+        ins = np.concatenate([j[5] for j in jobs])
+        # per source base two slots, the inserted base (if any) in front of the base itself (if kept): the read is the slots in use, in order
+        iv = [u8_values(j[6]) for j in jobs if j[6] is not None]
+        inserted = np.zeros(out.size, np.uint8)
+        if iv:
+            inserted[ins] = np.concatenate(iv)
+        slots = np.empty((out.size, 2), np.uint8)
+        slots[:, 0] = inserted
+        slots[:, 1] = out
+        used = np.empty((out.size, 2), bool)
+        used[:, 0] = ins
+        used[:, 1] = keep
+        res = np.take(acgt, np.compress(used.reshape(-1), slots.reshape(-1)))
+        rlen = np.array([j[7] for j in jobs], np.int64)
+        tlen = rlen + 17                    # ">pb%012d\n" + bases + "\n"
+        tend = np.cumsum(tlen); tbeg = tend - tlen
+        text = np.empty(int(tend[-1]), np.uint8)
+        seq = np.ones(text.size, bool)
+        hpos = (tbeg[:, None] + np.arange(16)).ravel()
+        seq[hpos] = False
+        seq[tend - 1] = False
+        text[hpos] = np.frombuffer(b"".join(b">pb%012d\n" % (first + i) for i in range(len(jobs))), np.uint8)
+        text[tend - 1] = 10
+        text[seq] = res
+        return text
+
+    md5 = hashlib.md5()
+    q = queue.Queue(maxsize=2 * threads)
+    err_box = []
+
+    def writer(fh):
+        while True:
+            f = q.get()
+            if f is None:
+                return
+            try:
+                t = f.result()
+                fh.write(t.data); md5.update(t.data)
+            except BaseException as e:      # surfaced by the main thread after the join
+                err_box.append(e)
+                return
+    mu = np.log(mean_len) - 0.5 * sigma * sigma
+    tot = nreads = 0
+    batch, batch_bp, first = [], 0, 0
+    with open(path, "wb") as fh, ThreadPoolExecutor(threads) as ex:
+        wt = threading.Thread(target=writer, args=(fh,))
+        wt.start()
+        try:
+            while tot < target and not err_box:
+                s_k = S.jump(s_at, k - k_at)
+                bg.state = {"bit_generator": "PCG64", "state": {"state": s_k, "inc": inc}, "has_uint32": h, "uinteger": w}
+                L = int(rng.lognormal(mu, sigma))
+                if L < min_len:
+                    L = min_len
+                if L > genome_len:
+                    L = genome_len
+                st = int(rng.integers(0, genome_len - L + 1))
+                rev = rng.random() < 0.5
+                now = bg.state
+                s_new, h, w = now["state"]["state"], now["has_uint32"], now["uinteger"]
+                s, n = s_k, 0
+                while s != s_new:
+                    s = (s * _PCG_MULT + inc) & _M128; n += 1
+                    if n > 4096:
+                        raise RuntimeError("synth_fasta: lost the position of the generator")
+                k += n; k_at, s_at = k, s_new
+                S.raw(k, L)
+                u = (S.flag(0, k, L), S.flag(1, k, L))      # random(L) < p_del, < p_del + p_sub
+                ndel = int(np.count_nonzero(u[0]))
+                nsub = int(np.count_nonzero(u[1])) - ndel
+                k += L
+                sv, k, h, w = u8(k, h, w, nsub, 1)
+                S.raw(k, L)
+                v = S.flag(2, k, L)                          # random(L) < p_ins
+                nins = int(np.count_nonzero(v))
+                k += L
+                iv, k, h, w = u8(k, h, w, nins, 0)
+                batch.append((st, L, rev, u, sv, v, iv, L - ndel + nins))
+                tot += L - ndel + nins
+                nreads += 1; batch_bp += L
+                if batch_bp >= (1 << 22):
+                    q.put(ex.submit(build, first, batch))
+                    first += len(batch); batch, batch_bp = [], 0
+            if batch and not err_box:
+                q.put(ex.submit(build, first, batch))
+        finally:
+            q.put(None)
+            wt.join()
+            S.close()
+    if err_box:
+        raise err_box[0]
+    return nreads, tot, md5.hexdigest()
+
+
 def gen_reads(path, genome, coverage, seed):
-    from smartdenovo_amd import synth
+    """the seeded read set (smartdenovo_amd/synth.py) as FASTA, made once per tmp dir; where tests/golden/big_manifest.json knows the set, its md5 must match"""
     if os.path.exists(path) and os.path.exists(path + ".meta"):
         return json.load(open(path + ".meta"))
-    names, seqs = synth.synth_reads(genome, coverage, seed=seed)
-    md5 = synth.write_fasta(path + ".tmp", names, seqs)
+    reads, bases, md5 = synth_fasta(path + ".tmp", genome, coverage, seed)
+    for name, s in json.load(open(os.path.join(ROOT, "tests", "golden", "big_manifest.json")))["sets"].items():
+        if (s["genome"], s["coverage"], s["seed"], s.get("repeats")) == (genome, coverage, seed, False) and s.get("md5_fasta") not in (None, md5):
+            os.remove(path + ".tmp")
+            raise RuntimeError("bench input %s: md5 %s, the set the goldens were made on has %s" % (name, md5, s["md5_fasta"]))
     os.replace(path + ".tmp", path)
-    meta = {"reads": len(names), "bases": int(sum(s.size for s in seqs)), "md5": md5}
+    meta = {"reads": reads, "bases": bases, "md5": md5}
     json.dump(meta, open(path + ".meta", "w"))
     return meta
+
+
+def dump_outputs(ddir, ovl, max_rows=600000, cigar_sample=2048):
+    """What the timed path hands its caller - the .ovl of the last step and its .contained list - as arrays under ddir (float32 / float64 .npy, < 64 MB):
+      ovl_records.npy   float32 [rows, 16]: the 16 leading columns of each record (read ids = the number in the synthetic name, strand 0 = '+', 1 = '-';
+                        lengths, coordinates, score, identity, matches, mismatches, insertions, deletions); every value but the identity is an exact integer
+      ovl_cigar.npy     float64 [rows, 2]: byte length and CRC-32 of the rest of the line (the CIGAR), exact
+      ovl_rows.npy      float64 [rows]: the record numbers these rows are (all of them, or a seeded sample when there are more than max_rows)
+      ovl_cigar_ops.npy float64 [m, 5]: record number, total M, I and D lengths and number of operations of the CIGARs of a seeded sample of m records
+      contained.npy     float64 [c]: ids of the reads written to .contained, in file order"""
+    import re
+    import zlib
+    import numpy as np
+    os.makedirs(ddir, exist_ok=True)
+    strand = {b"+": b"0", b"-": b"1"}
+    fields, cig, offs, off = [], [], [], 0
+    with open(ovl, "rb") as fh:
+        for line in fh:
+            offs.append(off); off += len(line)
+            p = line.rstrip(b"\n").split(b"\t", 16)
+            c = p[16] if len(p) > 16 else b""
+            cig.append((len(c), zlib.crc32(c)))
+            p[0], p[1], p[5], p[6] = p[0][2:], strand[p[1]], p[5][2:], strand[p[6]]
+            fields.extend(p[:16])
+    n = len(cig)
+    rows = np.arange(n) if n <= max_rows else np.sort(np.random.default_rng(20240611).choice(n, max_rows, replace=False))
+    rec = np.array(fields, dtype="S").astype(np.float64).reshape(n, 16)
+    np.save(os.path.join(ddir, "ovl_records.npy"), rec[rows].astype(np.float32))
+    np.save(os.path.join(ddir, "ovl_cigar.npy"), np.array(cig, dtype=np.float64).reshape(n, 2)[rows])
+    np.save(os.path.join(ddir, "ovl_rows.npy"), rows.astype(np.float64))
+    ops = []
+    with open(ovl, "rb") as fh:
+        for i in np.sort(np.random.default_rng(7).choice(n, min(n, cigar_sample), replace=False)):
+            fh.seek(offs[i])
+            p = fh.readline().rstrip(b"\n").split(b"\t", 16)
+            t = {b"M": 0, b"I": 0, b"D": 0}
+            m = re.findall(rb"(\d+)([MID])", p[16] if len(p) > 16 else b"")
+            for ln, op in m:
+                t[op] += int(ln)
+            ops.append((i, t[b"M"], t[b"I"], t[b"D"], len(m)))
+    np.save(os.path.join(ddir, "ovl_cigar_ops.npy"), np.array(ops, dtype=np.float64).reshape(-1, 5))
+    cont = [int(l.strip()[2:]) for l in open(ovl + ".contained", "rb") if l.strip()] if os.path.exists(ovl + ".contained") else []
+    np.save(os.path.join(ddir, "contained.npy"), np.array(cont, dtype=np.float64))
+    return n
 
 
 def cpu_baseline(engine_argv, genome, coverage, seed, tmp, same_input=False, threads=0, fa=None):
@@ -146,7 +455,7 @@ def cpu_baseline(engine_argv, genome, coverage, seed, tmp, same_input=False, thr
             lens[name] = len(line.strip())
     # the reference's index build is O(threads x bases) (every thread scans every read, wtzmo.c:272): on the 256-thread GPU host
     # -t 256 is 4x SLOWER than -t 32 (56 s vs 13.8 s on the full E. coli-shape set), so the baseline uses min(32, cores)
-    ncpu = threads or min(32, os.cpu_count() or 1)
+    ncpu = threads or min(32, usable_cpus())
     out = os.path.join(tmp, "cpu.ovl")
     if os.path.exists(ref):
         pairs = os.path.join(tmp, "cpu.pairs")
@@ -193,6 +502,9 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline", choices=["input", "sample"], default=None, help="reference wtzmo on the bench input itself (default where the workload has a golden) or on a bounded same-shape sample")
     ap.add_argument("--no-verify", action="store_true", help="skip the md5 comparison of the last step's .ovl with the reference golden (tests/golden/big_manifest.json)")
+    ap.add_argument("--full", action="store_true", help="also what the headline number does not need: the parity of the last step against the reference golden (or the "
+                    "reference stripe pass), the CPU baselines, the PMC traffic of the newest committed profile and the build id of the kernels")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed (its .ovl and .contained) as .npy arrays under DIR")
     a = ap.parse_args()
     wl = WORKLOADS[a.workload]
     a.genome = a.genome or wl["genome"]; a.coverage = a.coverage or wl["coverage"]; a.seed = a.seed or wl["seed"]
@@ -247,7 +559,9 @@ def main():
     fa = os.path.join(tmp, "reads_G%d_c%g_s%d.fa" % (a.genome, a.coverage, a.seed))
     meta = None
     if rank == 0:
+        t_in = time.perf_counter()
         meta = gen_reads(fa, a.genome, a.coverage, a.seed)
+        print("[bench] read set %s: %d reads, %d bp (%.1f s)" % (fa, meta["reads"], meta["bases"], time.perf_counter() - t_in), file=sys.stderr)
     if dist:
         dist.barrier()
     if meta is None:
@@ -393,13 +707,37 @@ def main():
     # (profiles/r03_valu_int32_ubench.txt): v_add / v_sub ~60 Tlane-op/s, v_max_i32 / v_alignbit / v_mad_i32_i24 / v_lshl_or ~36.6 (half rate)
     for key in ("roofline", "roofline_sw1", "roofline_sw2"):
         res[key]["peak_measured_Tops"] = {"v_add_u32": 63.5, "v_max_i32": 36.6}
+    if world > 1:
+        res["gathered_result_bytes_per_step"] = xchg.bytes_received // (W + K)
+        res["exchange_messages_per_step"] = xchg.messages // (W + K)
+        res["bytes_sent_from_device"] = sent_dev      # all ranks, all steps: > 0 iff the device-resident send path carried the text
+        res["backend"] = backend
+    if a.full:
+        add_full_figures(res, a, wl, rank, local, tmp, fa, eng, out, last, same_as_golden)
+    if a.engine == "dmo":       # no banded SW in the dot-matrix engine (SURVEY finding 2): its dominant kernel is K_pair, priced against HBM (after --full attached the PMC traffic)
+        res["roofline"] = dict(res["roofline_zmer"])
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, out)
+    print(json.dumps(res))
+    for leftover in (out, out + ".prev", out + ".contained"):
+        if os.path.exists(leftover):
+            os.remove(leftover)
+    if dist:
+        dist.destroy_process_group()
+
+
+def add_full_figures(res, a, wl, rank, local, tmp, fa, eng, out, last, same_as_golden):
+    """--full: what a plain run leaves out - the PMC traffic of the newest committed profile, the build id, the parity of the last step against the
+    reference (exit 1 on a mismatch) and the CPU baselines"""
+    import __graft_entry__ as ge
+    world = res["n_gpus"]
+    import csv
+    import glob
     # HBM traffic: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same command with --steps 1 --warmup 0 (so totals are per step),
     # condensed by tools/summarize_profiles.py into profiles/ (FETCH_SIZE doubled as the gfx950 guide says).  `traffic` is per LAUNCH like
     # `achieved` (total / dispatches), `traffic_per_step` the total next to the per-step algorithmic bytes.  A PMC pass cannot run inside a timed
     # bench run, so the numbers come from the newest committed summary of this workload / engine; its sidecar (<csv>.meta.json, written by
     # tools/gpu_r04_final.sh) names the kernel sources it was measured on, and the line says whether they are the sources of THIS build.
-    import csv
-    import glob
     cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_%s_%s_pmc_per_kernel.csv" % (a.workload, a.engine))))
     src = cands[-1] if cands else None
     ksrc_now = kernel_source_id()
@@ -430,11 +768,6 @@ def main():
         for key in ("roofline", "roofline_sw1", "roofline_sw2"):
             if res[key].get("traffic_per_step"):
                 res[key]["algorithmic_trace_bytes_per_step"] = res[key]["cells_per_step"]       # the reference's layout: 1 trace byte per cell
-    if world > 1:
-        res["gathered_result_bytes_per_step"] = xchg.bytes_received // (W + K)
-        res["exchange_messages_per_step"] = xchg.messages // (W + K)
-        res["bytes_sent_from_device"] = sent_dev      # all ranks, all steps: > 0 iff the device-resident send path carried the text
-        res["backend"] = backend
     # parity of THIS run: the last step's file against the md5 of reference `wtzmo -t 1` on the same input (generated once, committed)
     gold = None
     if wl.get("golden") and same_as_golden and not a.no_verify:
@@ -472,23 +805,15 @@ def main():
         try:
             same = (a.cpu_genome == a.genome)
             res["cpu_baseline"] = cpu_baseline(eng, a.cpu_genome, a.coverage, a.seed if same else a.seed + 1000, tmp, same_input=same, fa=fa if same else None)
-            res["cpu_baseline"]["threads_note"] = ("-t %d, not all %d hardware threads: the reference's index build is O(threads x bases) (every thread scans every read, wtzmo.c:272) - "
-                                                   "measured on this host, E. coli shape: -t 256 is 4x slower than -t 32" % (res["cpu_baseline"]["cores"], os.cpu_count() or 1))
-            if (os.cpu_count() or 1) > res["cpu_baseline"]["cores"]:
+            res["cpu_baseline"]["threads_note"] = ("-t %d = min(32, the %d CPUs this process may use): the reference's index build is O(threads x bases) (every thread scans every read, wtzmo.c:272) - "
+                                                   "measured on a 256-thread host, E. coli shape: -t 256 is 4x slower than -t 32" % (res["cpu_baseline"]["cores"], usable_cpus()))
+            if usable_cpus() > res["cpu_baseline"]["cores"]:
                 # north_star's "-t <all host cores>", stated too: on a bounded sample of the same shape (the full input at -t 256 runs for a quarter of an hour)
                 sg = a.cpu_genome if a.cpu_genome <= 1000000 else max(200000, a.genome // 20)
-                allc = cpu_baseline(eng, sg, a.coverage, a.seed + 1000, tmp, same_input=False, threads=os.cpu_count())
+                allc = cpu_baseline(eng, sg, a.coverage, a.seed + 1000, tmp, same_input=False, threads=usable_cpus())
                 res["cpu_baseline_all_cores"] = allc
         except Exception as e:      # the baseline is reported, never required
             res["cpu_baseline"] = {"value": None, "error": str(e)}
-    if a.engine == "dmo":       # no banded SW in the dot-matrix engine (SURVEY finding 2): its dominant kernel is K_pair, priced against HBM (after the PMC traffic was attached above)
-        res["roofline"] = dict(res["roofline_zmer"])
-    print(json.dumps(res))
-    for leftover in (out, out + ".prev", out + ".contained"):
-        if os.path.exists(leftover):
-            os.remove(leftover)
-    if dist:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -28,7 +28,7 @@ def test_two_ranks_over_rccl_write_the_reference_file(extra):
     if _device_count() < 2:
         pytest.skip("fewer than two visible GPUs: RCCL needs one device per rank")
     env = dict(os.environ, WTZ_BENCH_BACKEND="nccl", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "ecoli", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"] + extra,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "ecoli", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--full"] + extra,
                        capture_output=True, env=env, timeout=1800)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     line = json.loads(r.stdout.decode().strip().split("\n")[-1])
