@@ -17,6 +17,9 @@
  *                           kswx_extend_align_shift_core, ksw_global2) hzm_aln.h:1247-1486, kswx.h:101-335, ksw.c:503-586;
  *                           with params.refine also kswx_refine_alignment kswx.h:483-659
  *
+ *   wtz_local_batch      <- ksw_align2 with KSW_XSTART over ksw_i16         ksw.c:344-366, 233-335 (what kswx_align*, kswx.h:1495-1520, and
+ *                           wtcns.c:209, 269 call: the first step of wtcyc, pairaln and wtcns; no tool of this library uses it yet)
+ *
  *   wtz_pairs_seed + wtz_pairs_align with params.aux_strand = 1
  *                        <- align_hzmaux, the pair routine of wtgbo   hzm_aln.h:1684-1775 (its caller wtgbo.c:37-56 orients the read first:
  *                           the host uploads every read and its reverse complement, smartdenovo_amd/csrc/host/wtgbo_main.c)
@@ -101,6 +104,8 @@ typedef struct {
 	uint64_t bytes_zmer_algo;                                                         /* algorithmic bytes of z-mer matching: candidate L/4 + 16 B per emitted match (hzm_aln.h:173-224) */
 	double   ms_ingest;                                                               /* K_pack_ascii + K_pack_fix of wtz_upload_reads_ascii (kernel time, copies excluded) */
 	uint64_t bytes_ingest_algo;                                                       /* 1 byte read + 2 bits written per base */
+	double   ms_local;                                                                /* K-local of wtz_local_batch (kernel time, copies excluded) */
+	uint64_t n_local, cells_local;                                                    /* its problems and the DP cells (rows x columns of both passes) it executed */
 } wtz_counters_t;
 
 const char *wtz_last_error(void);
@@ -240,6 +245,20 @@ int  wtz_test_dp(wtz_ctx_t *ctx, int32_t kind, int32_t form, const wtz_dp_proble
  * The jobs go through the same dispatch as the end extensions of wtzmo's stitched alignments.  out[i] = the kswx_t of the call (score, qe, te, aln, mat, mis, ins, del;
  * an empty side returns the start score clamped at 0, like kswx.h:113-118) and cigar_off / cigar_len of its operations (len << 4 | op, first operation first) in `cigar`. */
 int  wtz_extend_batch(wtz_ctx_t *ctx, const wtz_dp_problem_t *problems, uint32_t n, wtz_dp_result_t *out, uint32_t *cigar, uint64_t cigar_cap);
+
+/* ksw_align2(qlen, query, tlen, target, 4, mat(M, X), o_del, e_del, o_ins, e_ins, KSW_XSTART, NULL) (ksw.c:344-366) for n independent problems on views of the
+ * uploaded reads: the full, unbanded local Smith-Waterman in the reference's 16-bit lanes (ksw_i16, ksw.c:233-335: the kswx callers never set KSW_XBYTE, so
+ * H saturates at 32767 like _mm_adds_epi16) and its second pass over the reversed prefixes for the start (ksw.c:358-364).  out[i] = the kswr_t fields as
+ * ksw_align2 returns them, inclusive and 0-based, before the callers' ++ (kswx.h:1508-1511): score, te = the smallest target row whose maximum reaches the
+ * score (ksw.c:308), qe = the smallest query column holding it (ksw.c:320-322), tb / qb from the second pass (-1 where its maximum differs from the score,
+ * ksw.c:363); a score of 0 gives te = -1, qe = 0, tb = qb = 0.  score2 / te2 are not computed (no kswx caller sets KSW_XSUBO).
+ * Problems are wtz_dp_problem_t views (q_rev / t_rev, q_from / t_from, q_strand / t_strand, q_len / t_len as for wtz_extend_batch); W and init_score are
+ * ignored.  M and X are the context's params (1 <= M <= 127, -128 <= X <= 0: the reference's int8 matrix), the four gap costs are >= 0 with open + extend <= 32767.
+ * LIMIT: 1 <= q_len, t_len <= 65535 per problem (one wavefront per problem); anything else is WTZ_E_ARG for the whole call, nothing is truncated and the
+ * context stays usable.  form_used = query columns per lane of the first pass (4 up to 256 columns, else 16), cells = rows x columns of both passes as
+ * executed.  The call takes 8 * t_len bytes of the main pool per problem whose query exceeds one strip (64 * form_used columns) and leaves the pool empty. */
+typedef struct { int32_t score, te, qe, tb, qb; uint32_t form_used; uint64_t cells; } wtz_local_result_t;
+int  wtz_local_batch(wtz_ctx_t *ctx, const wtz_dp_problem_t *problems, uint32_t n, int32_t o_del, int32_t e_del, int32_t o_ins, int32_t e_ins, wtz_local_result_t *out);
 
 /* Scratch accounting, so that the caller can size its batches to the pool instead of discovering the limit by WTZ_E_POOL:
  * the context's scratch is cut into a main pool (everything that lives for the batch: match lists, windows, CIGARs) and a transient

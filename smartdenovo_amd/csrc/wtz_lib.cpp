@@ -21,6 +21,7 @@
 #include "wtz_tasks.h"
 #include "wtz_sw_frame.h"
 #include "wtz_stitch_fused.h"
+#include "wtz_sw_local.h"
 
 /* ------------------------------------------------------------------------------------------------ */
 /* device abstraction                                                                               */
@@ -2319,6 +2320,83 @@ extern "C" int wtz_extend_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32
 		out[i] = o;
 	}
 	CHK(pool_check(c, "wtz_extend_batch"));
+	return WTZ_OK;
+}
+
+/* ------------------------------------------------------------------------------------------------ */
+/* local Smith-Waterman with start coordinates (the routine wtcyc, pairaln and wtcns start from)      */
+/* ------------------------------------------------------------------------------------------------ */
+/* ksw_align2(..., KSW_XSTART) with 16-bit lanes (ksw.c:344-366 over ksw_i16, ksw.c:233-335) for n independent problems on views of the uploaded reads:
+ * K-local (wtz_sw_local.h), one wavefront per problem, both passes on the same wavefront, largest problem first.  The strip-boundary column of a
+ * problem (two buffers of t_len words, only for queries of more than one strip) is planned on the host and taken from the main pool in one block. */
+struct K_local;
+extern "C" int wtz_local_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32_t n, int32_t o_del, int32_t e_del, int32_t o_ins, int32_t e_ins, wtz_local_result_t *out){
+	if(!c || !c->bits) return wtz_fail(WTZ_E_ARG, "reads not uploaded");
+	if(n == 0) return WTZ_OK;
+	if(!pr || !out) return wtz_fail(WTZ_E_ARG, "null argument");
+	if(n > 0x7FFFFFFFu) return wtz_fail(WTZ_E_ARG, "wtz_local_batch: more than 2^31 - 1 problems in one call");      /* one block per problem */
+	/* the value range of the 16-bit routine: scores as the reference's int8 matrix holds them (kswx.h:1495-1520 fills it from M / X), gap costs >= 0 (ksw.c:253-256) */
+	if(c->P.M < 1 || c->P.M > 127 || c->P.X > 0 || c->P.X < -128) return wtz_fail(WTZ_E_ARG, "wtz_local_batch: M must be in [1, 127] and X in [-128, 0]");
+	if(o_del < 0 || e_del < 0 || o_ins < 0 || e_ins < 0 || (int64_t)o_del + e_del > 32767 || (int64_t)o_ins + e_ins > 32767) return wtz_fail(WTZ_E_ARG, "wtz_local_batch: gap costs must be >= 0 and open + extend <= 32767");
+	CTX_ENTER(c);
+	CHK(pool_reset(c));
+	std::vector<uint64_t> h_off(c->n_reads);
+	CHK(dev_d2h(h_off.data(), c->rdoff, (size_t)c->n_reads * 8));
+	std::vector<wtz_locprob_t> hp(n);
+	unsigned long long bnd_words = 0;
+	for(uint32_t i = 0; i < n; i++){
+		const wtz_dp_problem_t &p = pr[i];
+		if(p.q_read >= c->n_reads || p.t_read >= c->n_reads) return wtz_fail(WTZ_E_ARG, "problem %u: read id out of range", i);
+		if((p.q_strand != 1 && p.q_strand != -1) || (p.t_strand != 1 && p.t_strand != -1)) return wtz_fail(WTZ_E_ARG, "problem %u: strand must be +1 or -1", i);
+		if(p.q_len < 1 || p.t_len < 1) return wtz_fail(WTZ_E_ARG, "problem %u: empty sequence", i);
+		if(p.q_len > WTZ_LOC_MAXLEN || p.t_len > WTZ_LOC_MAXLEN) return wtz_fail(WTZ_E_ARG, "problem %u: %d x %d is beyond the %d x %d of one wavefront", i, p.t_len, p.q_len, WTZ_LOC_MAXLEN, WTZ_LOC_MAXLEN);
+		wtz_readview vq, vt;
+		vq.bits = c->bits; vq.off = h_off[p.q_read]; vq.len = c->h_rdlen[p.q_read]; vq.rev = p.q_rev ? 1u : 0u;
+		vt.bits = c->bits; vt.off = h_off[p.t_read]; vt.len = c->h_rdlen[p.t_read]; vt.rev = p.t_rev ? 1u : 0u;
+		const int64_t qlast = (int64_t)p.q_from + (int64_t)p.q_strand * (p.q_len - 1), tlast = (int64_t)p.t_from + (int64_t)p.t_strand * (p.t_len - 1);
+		if(p.q_from < 0 || p.q_from >= (int64_t)vq.len || qlast < 0 || qlast >= (int64_t)vq.len || p.t_from < 0 || p.t_from >= (int64_t)vt.len || tlast < 0 || tlast >= (int64_t)vt.len)
+			return wtz_fail(WTZ_E_ARG, "problem %u: region outside its read", i);
+		wtz_locprob_t d; d.q = vq.sub(p.q_from, p.q_strand); d.t = vt.sub(p.t_from, p.t_strand); d.qlen = p.q_len; d.tlen = p.t_len; d.bnd_off = bnd_words;
+		if(p.q_len > wtz_loc_strip_cols(p.q_len)) bnd_words += 2ull * (unsigned long long)p.t_len;      /* more than one strip: on the device, more than 1 024 columns */
+		hp[i] = d;
+	}
+	std::vector<uint32_t> order(n);
+	for(uint32_t i = 0; i < n; i++) order[i] = i;
+	std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b){ return (uint64_t)hp[a].qlen * (uint64_t)hp[a].tlen > (uint64_t)hp[b].qlen * (uint64_t)hp[b].tlen; });
+	wtz_locprob_t *d_pr = NULL; uint32_t *d_order = NULL; wtz_locres_t *d_res = NULL; uint32_t *d_bnd = NULL;
+	CHK(dev_alloc((void**)&d_pr, (size_t)n * sizeof(wtz_locprob_t))); CHK(dev_h2d(d_pr, hp.data(), (size_t)n * sizeof(wtz_locprob_t)));
+	CHK(dev_alloc((void**)&d_order, (size_t)n * 4)); CHK(dev_h2d(d_order, order.data(), (size_t)n * 4));
+	CHK(dev_alloc((void**)&d_res, (size_t)n * sizeof(wtz_locres_t))); CHK(dev_set(d_res, 0, (size_t)n * sizeof(wtz_locres_t)));
+	if(bnd_words){
+		if(bnd_words * 4ull > c->main_bytes){ c->last_pool_fail = 1; return wtz_fail(WTZ_E_POOL, "wtz_local_batch: %llu bytes of strip boundaries in a main pool of %llu; use fewer problems per call or a larger pool", bnd_words * 4ull, (unsigned long long)c->main_bytes); }
+		if(pool_alloc_host(c, 0, (size_t)bnd_words * 4, (void**)&d_bnd) != WTZ_OK){      /* the pool's own rounding on top of a request that just fitted */
+			c->last_pool_fail = 1;
+			return wtz_fail(WTZ_E_POOL, "wtz_local_batch: no room for %llu bytes of strip boundaries in the main pool; use fewer problems per call or a larger pool", bnd_words * 4ull);
+		}
+	}
+	wtz_locsc_t S; S.M = c->P.M; S.X = c->P.X; S.oe_del = o_del + e_del; S.e_del = e_del; S.oe_ins = o_ins + e_ins; S.e_ins = e_ins;
+	wtz_timer tm; tm.start();
+#ifndef WTZ_EMUL
+	hipLaunchKernelGGL(wtz_kernel_local, dim3(n), dim3(64), 0, g_stream, (const wtz_locprob_t*)d_pr, (const uint32_t*)d_order, n, S, d_bnd, d_res);
+	HIPCHK(hipGetLastError());
+#else
+	for(uint32_t b = 0; b < n; b++){ const uint32_t id = d_order[b]; wtz_local_problem(d_pr[id], S, d_bnd, d_res[id]); }
+#endif
+	CHK(dev_sync());
+	c->cnt.ms_local += tm.stop();
+	std::vector<wtz_locres_t> hr(n);
+	CHK(dev_d2h(hr.data(), d_res, (size_t)n * sizeof(wtz_locres_t)));
+	for(uint32_t i = 0; i < n; i++){
+		wtz_local_result_t o; memset(&o, 0, sizeof o);
+		o.score = hr[i].score; o.te = hr[i].te; o.qe = hr[i].qe; o.tb = hr[i].tb; o.qb = hr[i].qb; o.form_used = hr[i].form; o.cells = hr[i].cells;
+		c->cnt.cells_local += hr[i].cells;
+		out[i] = o;
+	}
+	c->cnt.n_local += n;
+	CHK(pool_check(c, "wtz_local_batch"));
+	/* nothing of the call lives on: the main pool goes back empty (wtz_pool_info shows main_used = 0; the bytes taken are in counters.pool_peak) */
+	CHK(pool_reset(c));
+	c->main_used_call = 0;
 	return WTZ_OK;
 }
 

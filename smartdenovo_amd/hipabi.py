@@ -17,7 +17,7 @@ SYMBOLS = [
     "wtz_last_error", "wtz_device_count", "wtz_device_memory", "wtz_ctx_create", "wtz_ctx_destroy", "wtz_ctx_clone", "wtz_upload_reads",
     "wtz_index_build", "wtz_zindex_build", "wtz_candidates", "wtz_candidates_begin", "wtz_candidates_end", "wtz_batch_begin", "wtz_pairs_seed",
     "wtz_pairs_windows", "wtz_pairs_align", "wtz_fetch_cigars", "wtz_fetch_cigar_text", "wtz_fetch_cigar_text_begin", "wtz_fetch_cigar_text_end", "wtz_cigar_text_device", "wtz_host_alloc", "wtz_host_free", "wtz_get_counters", "wtz_reset_counters",
-    "wtz_test_dp", "wtz_extend_batch", "wtz_pool_info", "wtz_pool_failure_kind",
+    "wtz_test_dp", "wtz_extend_batch", "wtz_local_batch", "wtz_pool_info", "wtz_pool_failure_kind",
     "wtz_index_count", "wtz_index_counts_fetch", "wtz_index_finish", "wtz_candidate_groups_begin", "wtz_candidate_groups_end", "wtz_candidate_groups_fetch", "wtz_cand_tail_host", "wtz_zindex_build_subset", "wtz_zindex_build_queries", "wtz_upload_reads_ascii", "wtz_fetch_read_bits", "wtz_append_revcomp_views",
 ]
 
@@ -62,6 +62,8 @@ DP_PROBLEM = np.dtype([("q_read", "<u4"), ("t_read", "<u4"), ("q_rev", "<u4"), (
 DP_RESULT = np.dtype([("score", "<i4"), ("tb", "<i4"), ("te", "<i4"), ("qb", "<i4"), ("qe", "<i4"), ("aln", "<i4"), ("mat", "<i4"),
                       ("mis", "<i4"), ("ins", "<i4"), ("del", "<i4"), ("cigar_len", "<u4"), ("form_used", "<u4"), ("cigar_off", "<u8"), ("cells", "<u8")])
 DP_SHIFT, DP_FIXED, DP_GLOBAL = 0, 1, 2
+LOCAL_RESULT = np.dtype([("score", "<i4"), ("te", "<i4"), ("qe", "<i4"), ("tb", "<i4"), ("qb", "<i4"), ("form_used", "<u4"), ("cells", "<u8")])
+LOCAL_MAXLEN = 65535      # rows / columns of one wtz_local_batch problem (include/wtzmo_hip.h)
 
 
 class Counters(C.Structure):
@@ -69,7 +71,8 @@ class Counters(C.Structure):
                [(n, C.c_uint64) for n in ("n_candidates_q", "n_pairs", "n_winalign", "n_stitch", "cells_shift", "cells_fixed",
                                           "cells_global", "bytes_seed_algo", "pool_peak")] + \
                [("ms_ext", C.c_double), ("n_extjobs", C.c_uint64), ("ms_gap", C.c_double), ("bytes_zmer_algo", C.c_uint64),
-                ("ms_ingest", C.c_double), ("bytes_ingest_algo", C.c_uint64)]
+                ("ms_ingest", C.c_double), ("bytes_ingest_algo", C.c_uint64),
+                ("ms_local", C.c_double), ("n_local", C.c_uint64), ("cells_local", C.c_uint64)]
 
 
 def load(path: str | None = None) -> C.CDLL:
@@ -214,6 +217,14 @@ class Context:
         cig = np.zeros(cigar_cap, dtype=np.uint32)
         self._chk(self.lib.wtz_test_dp(self.h, kind, form, problems.ctypes.data, problems.size, out.ctypes.data, cig.ctypes.data, cig.size))
         return out, [cig[int(o):int(o) + int(n)].copy() for o, n in zip(out["cigar_off"], out["cigar_len"])]
+
+    def local_batch(self, problems, o_del, e_del, o_ins, e_ins):
+        """ksw_align2(..., KSW_XSTART) per problem (wtz_local_batch): score, te, qe, tb, qb as the reference returns them."""
+        problems = np.ascontiguousarray(problems, dtype=DP_PROBLEM)
+        out = np.zeros(problems.size, dtype=LOCAL_RESULT)
+        self.lib.wtz_local_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+        self._chk(self.lib.wtz_local_batch(self.h, problems.ctypes.data, problems.size, o_del, e_del, o_ins, e_ins, out.ctypes.data))
+        return out
 
     def counters(self) -> Counters:
         c = Counters()
