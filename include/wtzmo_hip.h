@@ -218,7 +218,8 @@ void  wtz_host_free(void *p);
  *        WTZ_DP_FIXED  <- kswx_extend_align_core       kswx.h:234-335   (band = params.w, as the path always calls it)
  *        WTZ_DP_GLOBAL <- ksw_global2                  ksw.c:503-586    (W = band width of this ONE call; gap costs from params)
  *   form 0 = the form the product would pick (for WTZ_DP_SHIFT: the whole run_extjobs dispatch); otherwise
- *        WTZ_DP_SHIFT : 1 one-wave register kernel, 2 four-wave kernel, 3 LDS-ring kernel (+ its scalar fallback), 4 scalar body
+ *        WTZ_DP_SHIFT : 3 LDS-ring kernel (+ its scalar fallback), 4 scalar body, 5 one-wave kernel in the anti-diagonal frame, 7 the same with two 16-bit cells
+ *                       per register; 1, 2 and 6 were kernels that have been removed: their numbers are not reused, the call returns WTZ_E_ARG
  *        WTZ_DP_FIXED / WTZ_DP_GLOBAL : C | 16*pool  (C = 1, 2, 4, 8 band columns per lane; +16 = 4-bit trace in the pool instead of LDS),
  *                       255 scalar body; WTZ_DP_GLOBAL also 32 = LDS-ring wave DP, 33 = the same with the 72 KB slice of the wide launch
  *   out[i].form_used = the form that produced the result, 0 = the forced form does not cover this problem (result untouched). */

@@ -4,7 +4,7 @@
  *
  * Host (wtext_core.h, plain C): inputs, the clipping and re-scoring of every overlap's CIGAR, the order of the records.
  * Device (libwtzmo_hip.so, wtz_extend_batch): every end extension - kswx_extend_align (kswx.h:469-481) is kswx_extend_align_shift_core, the K-sw3
- * routine of wtzmo's stitched alignments; the jobs of a block go through the same dispatch (register DP on one / four wavefronts per job).
+ * routine of wtzmo's stitched alignments; the jobs of a block go through the same dispatch (register DP on one wavefront per job).
  * There is no CPU implementation of the extension in this program: without a HIP device it exits with an error.
  */
 #define _GNU_SOURCE

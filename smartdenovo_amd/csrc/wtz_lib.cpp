@@ -35,10 +35,6 @@ static int wtz_fail(int code, const char *fmt, ...){
 	return code;
 }
 
-#ifndef WTZ_CAND_LDS_BYTES
-#define WTZ_CAND_LDS_BYTES 16384u     /* LDS window of the candidate-tuple sort */
-#endif
-static_assert((WTZ_CAND_LDS_BYTES & (WTZ_CAND_LDS_BYTES - 1u)) == 0u && WTZ_CAND_LDS_BYTES >= 4096u, "the windowed bitonic sort of K_candidates needs a power-of-two LDS window");
 #ifndef WTZ_PAIR_DM_LDS_TIER2
 #define WTZ_PAIR_DM_LDS_TIER2 49152u
 #endif
@@ -53,8 +49,6 @@ static_assert((WTZ_CAND_LDS_BYTES & (WTZ_CAND_LDS_BYTES - 1u)) == 0u && WTZ_CAND
 #define WTZ_PAIR_DM_LDS_TIER4 36864u
 #endif
 /* kernel name tags (rocprofv3 shows wtz_kernel_*<K_pair, ...>) */
-struct K_candidates;
-struct K_candidates_stream;
 struct K_candidates_wg;
 struct K_extjob_scalar;
 struct K_cigar_text;
@@ -93,7 +87,6 @@ struct K_stitch_fin;
 struct K_stitch_left;
 struct K_stitch_mid;
 struct K_winalign;
-struct K_winalign4;
 struct K_winalign_big;
 struct K_zfill; struct K_zread;
 struct K_zrun;
@@ -202,21 +195,6 @@ template<typename TAG, typename F> static int wtz_launch_wg(uint64_t n, F f, uin
 	if(n > 0x7FFFFFFFull) return wtz_fail(WTZ_E_ARG, "grid too large");
 	if(lds_bytes > 65536u){ HIPCHK(hipFuncSetAttribute((const void*)&wtz_kernel_wg_tasks<TAG, F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)); }
 	hipLaunchKernelGGL((wtz_kernel_wg_tasks<TAG, F>), dim3((uint32_t)n), dim3(nthreads), lds_bytes, g_stream, n, f);
-	HIPCHK(hipGetLastError());
-	return WTZ_OK;
-}
-/* four tasks per wavefront: one per 16-lane group (wtz_sw_grp.h); f gets the index of the block's first task */
-template<typename TAG, typename F> __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8))) wtz_kernel_grp_tasks(uint64_t n, F f){
-	const uint64_t i = (uint64_t)blockIdx.x * 4;
-	WTZ_PROF_BEGIN();
-	if(i < n) f(i);
-	WTZ_PROF_END();
-}
-template<typename TAG, typename F> static int wtz_launch_grp(uint64_t n, F f, uint32_t lds_bytes){
-	if(n == 0) return WTZ_OK;
-	const uint64_t nb = (n + 3) / 4;
-	if(nb > 0x7FFFFFFFull) return wtz_fail(WTZ_E_ARG, "grid too large");
-	hipLaunchKernelGGL((wtz_kernel_grp_tasks<TAG, F>), dim3((uint32_t)nb), dim3(64), lds_bytes, g_stream, n, f);
 	HIPCHK(hipGetLastError());
 	return WTZ_OK;
 }
@@ -378,7 +356,7 @@ struct wtz_ctx {
 	} zs[2];
 #ifndef WTZ_EMUL
 	hipStream_t stream;
-	hipStream_t stream_mw = 0; hipEvent_t ev_mw_fork = 0, ev_mw_join = 0;      /* side stream of the multi-wave K-sw3 launch */
+	hipStream_t stream_side = 0; hipEvent_t ev_side_fork = 0, ev_side_join = 0;      /* side stream of the fused K-sw3 stage: the items dealt to the 32-bit frame form run on it beside the packed launch (run_stitch_fused) */
 	hipStream_t stream_gap = 0; hipEvent_t ev_gap_fork = 0, ev_gap_join = 0;   /* side stream of K_gap (runs beside the left extensions) */
 #endif
 	bool shares_indexes;      /* clone: reads / k-mer table / z-index belong to the parent context */
@@ -423,24 +401,16 @@ struct wtz_ctx {
 	int last_pool_fail = 0;      /* which pool the last WTZ_E_POOL came from: 1 = main, 2 = transient (wtz_pool_failure_kind) */
 	double ext_use_ratio = 0.4; uint64_t tpool_last_used = 0;      /* run_stitch_fused: share of the trace upper bounds the fused launches have really taken */
 	bool fused_ran = false;      /* this stitch stage's fused launch has run: the extension launches behind it only sweep up what it left open */
-	int env_ext_mw_rows = 0;     /* WTZ_EXT_MW_ROWS=<n>: items whose two extensions can run at least n rows go to the four-wave frame kernel (wtz_sw_frame_mw.h) beside the fused launch.
-	                              * Off by default: measured at configs[2] (gpurun_out/r06d) K-sw3 418 ms without it, 490 ms with n = 2048 (1 000 of 30 000 items per range), 654 ms with
-	                              * n = 1024, 418 ms with n = 4096 (5-8 items per range) - the launches are bound by the row RATE of the resident wavefronts (time = ~5 ms + 0.65 ms per
-	                              * million rows), not by their longest job, and four wavefronts spend 2.2 x the instructions of one on a row */
 	int env_ext_pk = 1;          /* WTZ_EXT_PK=0: K-sw3 without the packed 16-bit form (wtz_sw_frame16.h) in front of the 32-bit frame form */
 	unsigned long long ext_fr_total = 0;        /* items dealt to the 32-bit form before the launch (geometry outside the 16-bit window) */
 	unsigned long long ext_open_total = 0;      /* items the packed form declined (outside its 16-bit window) and the 32-bit form finished */
-	int env_ext_fr = 1;          /* WTZ_EXT_FR=0: K-sw3 one-wave jobs on the round-4 register kernel (wtz_extend_shift_reg) instead of the frame form (wtz_sw_frame.h) */
 	int env_heavy_first = -1;    /* WTZ_PAIR_HEAVY_FIRST: the heaviest pairs of a K_pair launch first (-1 = engine default: dmo on, zmo off) */
-	int env_cand_wg = 1;         /* WTZ_CAND_WG=0: the one-wavefront-per-query sorting form of the seed lookup (the form before round 3) */
-	int env_cand_stream = 0;     /* WTZ_CAND_STREAM=1: sort-free candidate accumulation (LDS sketch + survivor table, wtz_seed.h); bit-exact, pays at 25x coverage only: see DESIGN.md */
 	int env_gap_lane = 1;        /* WTZ_GAP_LANE=0: every gap on a wavefront (the form before round 3) */
 	int env_lane = 1;            /* WTZ_WINALIGN_LANE=0: the chained wave-per-window kernel for every window (the form before round 3); 2: run both and compare */
-	int env_grp4 = 0;            /* WTZ_WINALIGN4=1: four windows per wavefront first (wtz_sw_grp.h; bit-exact, measured 2x SLOWER than one window per wave: see DESIGN.md) */
 	bool env_trace = false;      /* WTZ_STAGE_TRACE: name every device stage on stderr before it is launched (locating a device fault) */
 	bool env_fail_once = false;      /* WTZ_POOL_FAIL_ONCE: the injected failure hits one stage call only (the retry must then succeed) */
 	unsigned env_fail_at = 0, env_tfail_at = 0;      /* WTZ_POOL_FAIL_AT / WTZ_TPOOL_FAIL_AT: fault injection into the main / transient pool */
-	int env_dm_first_big = 1; int env_sw_mode = 0, env_use_reg = 1, env_gap_side = 0; bool env_profile = false;     /* WTZ_* debugging switches, read in wtz_ctx_create */
+	int env_dm_first_big = 1; int env_sw_mode = 0, env_gap_side = 0; bool env_profile = false;     /* WTZ_* debugging switches, read in wtz_ctx_create */
 };
 
 #ifndef WTZ_EMUL
@@ -553,31 +523,23 @@ extern "C" int wtz_ctx_create(int device, const wtz_params_c *params, uint64_t p
 #ifndef WTZ_EMUL
 	/* every failure from here on unwinds through wtz_ctx_destroy (all fields are initialised; it skips what does not exist yet) */
 	if(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess
-			|| hipStreamCreateWithFlags(&c->stream_mw, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&c->ev_mw_fork, hipEventDisableTiming) != hipSuccess
-			|| hipEventCreateWithFlags(&c->ev_mw_join, hipEventDisableTiming) != hipSuccess
+			|| hipStreamCreateWithFlags(&c->stream_side, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&c->ev_side_fork, hipEventDisableTiming) != hipSuccess
+			|| hipEventCreateWithFlags(&c->ev_side_join, hipEventDisableTiming) != hipSuccess
 			|| hipStreamCreateWithFlags(&c->stream_gap, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&c->ev_gap_fork, hipEventDisableTiming) != hipSuccess
 			|| hipEventCreateWithFlags(&c->ev_gap_join, hipEventDisableTiming) != hipSuccess){ wtz_ctx_destroy(c); return wtz_fail(WTZ_E_HIP, "hipStreamCreate / hipEventCreate failed"); }
 	g_stream = c->stream;
 	/* debugging switches are read once per context, not lazily from worker threads */
 	c->env_sw_mode = 0; if(getenv("WTZ_SW_SCALAR") && atoi(getenv("WTZ_SW_SCALAR"))) c->env_sw_mode = 1; if(getenv("WTZ_SW_CHECK") && atoi(getenv("WTZ_SW_CHECK"))) c->env_sw_mode = 2;
-	/* round 5: 0 = one wave per job always.  With the frame form at two waves per SIMD and the pool's counter sharded, the four-wave kernel (2.7x the SIMD time per row
-	 * for 1.5x the speed of one job) only costs throughput: K-sw3 stage at configs[2] 729 ms with the long jobs (>= 512 rows) on four waves, 692 with >= 2048, 612 with none */
-	c->env_use_reg = !(getenv("WTZ_SW_NOREG") && atoi(getenv("WTZ_SW_NOREG")));
 	c->env_gap_side = (getenv("WTZ_GAP_SIDESTREAM") && atoi(getenv("WTZ_GAP_SIDESTREAM"))) ? 1 : 0;
 	c->env_profile = getenv("WTZ_PROFILE_PAIR") != NULL;
 	if(getenv("WTZ_DM_FIRST_BIG")) c->env_dm_first_big = atoi(getenv("WTZ_DM_FIRST_BIG"));
 #endif
 	c->env_trace = getenv("WTZ_STAGE_TRACE") != NULL;
-	c->env_cand_stream = (getenv("WTZ_CAND_STREAM") && atoi(getenv("WTZ_CAND_STREAM")) != 0);
-	if(getenv("WTZ_CAND_WG")) c->env_cand_wg = atoi(getenv("WTZ_CAND_WG"));
 	if(getenv("WTZ_PAIR_HEAVY_FIRST")) c->env_heavy_first = atoi(getenv("WTZ_PAIR_HEAVY_FIRST"));
-	if(getenv("WTZ_EXT_FR")) c->env_ext_fr = atoi(getenv("WTZ_EXT_FR"));
 	if(getenv("WTZ_EXT_PK")) c->env_ext_pk = atoi(getenv("WTZ_EXT_PK"));
-	if(getenv("WTZ_EXT_MW_ROWS")) c->env_ext_mw_rows = atoi(getenv("WTZ_EXT_MW_ROWS"));
 	if(getenv("WTZ_EXT_FUSED")) c->env_ext_fused = atoi(getenv("WTZ_EXT_FUSED"));
 	if(getenv("WTZ_ZREAD")) c->env_zread = atoi(getenv("WTZ_ZREAD"));
 	if(getenv("WTZ_XCD_GROUP")) c->env_xcd_group = (uint32_t)atoi(getenv("WTZ_XCD_GROUP"));
-	c->env_grp4 = (getenv("WTZ_WINALIGN4") && atoi(getenv("WTZ_WINALIGN4")) != 0);
 	if(getenv("WTZ_WINALIGN_LANE")) c->env_lane = atoi(getenv("WTZ_WINALIGN_LANE"));
 	if(getenv("WTZ_GAP_LANE")) c->env_gap_lane = atoi(getenv("WTZ_GAP_LANE"));
 	c->env_fail_once = getenv("WTZ_POOL_FAIL_ONCE") != NULL;
@@ -687,10 +649,10 @@ extern "C" void wtz_ctx_destroy(wtz_ctx_t *c){
 	if(!c->shares_indexes){ dev_free_persist(c->bits); dev_free_persist(c->rdoff); dev_free_persist(c->rdlen); }
 	dev_free_persist(c->dP); dev_free_persist(c->dpool); dev_free_persist(c->pool_base);
 #ifndef WTZ_EMUL
-	if(c->stream_mw) (void)hipStreamDestroy(c->stream_mw);
+	if(c->stream_side) (void)hipStreamDestroy(c->stream_side);
 	if(c->stream_gap) (void)hipStreamDestroy(c->stream_gap);
 	if(c->stream_copy){ (void)hipStreamSynchronize(c->stream_copy); (void)hipStreamDestroy(c->stream_copy); if(c->ev_text_ready) (void)hipEventDestroy(c->ev_text_ready); for(int k = 0; k < 2; k++) if(c->ev_text_done[k]) (void)hipEventDestroy(c->ev_text_done[k]); }
-	{ hipEvent_t evs[4] = { c->ev_mw_fork, c->ev_mw_join, c->ev_gap_fork, c->ev_gap_join }; for(int k = 0; k < 4; k++) if(evs[k]) (void)hipEventDestroy(evs[k]); }
+	{ hipEvent_t evs[4] = { c->ev_side_fork, c->ev_side_join, c->ev_gap_fork, c->ev_gap_join }; for(int k = 0; k < 4; k++) if(evs[k]) (void)hipEventDestroy(evs[k]); }
 	if(c->stream) (void)hipStreamDestroy(c->stream);
 #endif
 	delete c;
@@ -1173,7 +1135,7 @@ extern "C" int wtz_candidates_begin(wtz_ctx_t *c, const uint32_t *qids, uint32_t
 	uint32_t *d_q = c->cq_q, *d_n = c->cq_nc; uint64_t *d_cand = c->cq_cand; unsigned long long *d_bytes = c->cq_bytes;
 	CHK(dev_h2d(d_q, qids, (size_t)nq * 4)); CHK(dev_h2d(d_n, ncand_in, (size_t)nq * 4)); CHK(dev_h2d(d_cand, cand, (size_t)nq * stride * 8));
 	CHK(dev_set(d_bytes, 0, 8));
-	const uint32_t *d_thr = NULL; (void)d_thr;
+	const uint32_t *d_thr = NULL;
 	if(c->idx_len_sorted && c->idx_end > c->idx_beg){
 		/* per query: the first indexed read that is NOT longer than 1.2 x the query (lengths are non-increasing in the id) */
 		std::vector<uint32_t> thr(nq);
@@ -1189,29 +1151,14 @@ extern "C" int wtz_candidates_begin(wtz_ctx_t *c, const uint32_t *qids, uint32_t
 	const uint32_t *seeds = c->kseeds; wtz_pool_t *pool = c->dpool;
 	STAGE(c, "K_candidates");
 	c->cq_tm.start();
-	if(c->env_cand_wg && !c->env_cand_stream){
-		/* one workgroup per query: partition by target read, sort each bucket in LDS (wtz_task_candidates_wg) */
-		const uint32_t key_hi = c->idx_end << 1;
+	/* one workgroup per query: partition by target read, sort each bucket in LDS (wtz_task_candidates_wg) */
+	const uint32_t key_hi = c->idx_end << 1;
 #ifdef WTZ_EMUL
-		static thread_local uint32_t emul_cwg_lds[WTZ_CWG_LDS_BYTES / 4 + 16];
-		uint32_t *lds_emul = emul_cwg_lds;
-		CHK(wtz_launch_wg<K_candidates_wg>(nq, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_candidates_wg((uint32_t)t, R, d_q, dP, tab, kmask, seeds, pool, d_cand, d_n, stride, d_bytes, lds_emul, d_thr, key_hi); }, 1u, 0u));
+	static thread_local uint32_t emul_cwg_lds[WTZ_CWG_LDS_BYTES / 4 + 16];
+	uint32_t *lds_emul = emul_cwg_lds;
+	CHK(wtz_launch_wg<K_candidates_wg>(nq, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_candidates_wg((uint32_t)t, R, d_q, dP, tab, kmask, seeds, pool, d_cand, d_n, stride, d_bytes, lds_emul, d_thr, key_hi); }, 1u, 0u));
 #else
-		CHK(wtz_launch_wg<K_candidates_wg>(nq, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_candidates_wg((uint32_t)t, R, d_q, dP, tab, kmask, seeds, pool, d_cand, d_n, stride, d_bytes, (uint32_t*)wtz_wave_scratch(), d_thr, key_hi); }, WTZ_CWG_THREADS, WTZ_CWG_LDS_BYTES));
-#endif
-	} else
-#ifndef WTZ_EMUL
-	{
-		/* LDS per wave: the group table + output list + heap row of the streaming form (the sorting form of a query with too many groups
-		 * uses the largest power-of-two window inside it) */
-		uint32_t lds_b = c->env_cand_stream ? (WTZ_CAND_STREAM_LDS_BYTES(c->P.ncand) + 15u) & ~15u : WTZ_CAND_LDS_BYTES;
-		if(lds_b < WTZ_CAND_LDS_BYTES || lds_b > 64u * 1024u) lds_b = WTZ_CAND_LDS_BYTES;
-		if(lds_b != WTZ_CAND_LDS_BYTES) CHK(wtz_launch_coop<K_candidates_stream>(0, nq, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_candidates<true>((uint32_t)t, R, d_q, dP, tab, kmask, seeds, pool, d_cand, d_n, stride, d_bytes, (uint64_t*)wtz_wave_scratch(), lds_b / 8, d_thr); }, lds_b));
-		/* the LDS window of the sorting form is a COMPILE-TIME constant: as a run-time value the windowed bitonic network loses its constant strides (26 -> 34 ms) */
-		else CHK(wtz_launch_coop<K_candidates>(0, nq, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_candidates<false>((uint32_t)t, R, d_q, dP, tab, kmask, seeds, pool, d_cand, d_n, stride, d_bytes, (uint64_t*)wtz_wave_scratch(), WTZ_CAND_LDS_BYTES / 8, (const uint32_t*)NULL); }, WTZ_CAND_LDS_BYTES));
-	}
-#else
-	CHK(wtz_launch_coop<K_candidates>(0, nq, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_candidates<false>((uint32_t)t, R, d_q, dP, tab, kmask, seeds, pool, d_cand, d_n, stride, d_bytes, (uint64_t*)NULL, 0); }));
+	CHK(wtz_launch_wg<K_candidates_wg>(nq, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_candidates_wg((uint32_t)t, R, d_q, dP, tab, kmask, seeds, pool, d_cand, d_n, stride, d_bytes, (uint32_t*)wtz_wave_scratch(), d_thr, key_hi); }, WTZ_CWG_THREADS, WTZ_CWG_LDS_BYTES));
 #endif
 	c->cq_tm.lap();
 	c->cq_pending = true;
@@ -1538,7 +1485,8 @@ WTZ_HD uint64_t wtz_ext_trace_need(int32_t qlen, int32_t tlen, int32_t init, int
 	wtz_ext_geometry(qlen, tlen, init, W, M, O, O, E, T, ql, tl, n_col);
 	if(ql_out) *ql_out = ql;
 	if(ncol_out) *ncol_out = n_col;
-	/* one-wave register kernel (4-column steps), four-wave kernel (256 lanes), LDS-ring kernel (odd columns per lane) */
+	/* row bytes: the widest of the one-wave register forms (4-column steps), a 256-lane row (the layout of the removed four-wave kernels) and the LDS-ring kernel
+	 * (odd columns per lane).  The 256-lane term stays: the launch groups and ext_use_ratio are calibrated against this bound, and it changes no result */
 	const uint64_t c_reg = ((uint64_t)(n_col + 63) / 64 + 3) / 4, c_mw = ((uint64_t)(n_col + 255) / 256 + 3) / 4 * 4, c_gen = ((((uint64_t)(n_col + 63) / 64) | 1) + 3) / 4;
 	uint64_t zrow = (c_reg > c_gen ? c_reg : c_gen) * 256; if(c_mw * 256 > zrow) zrow = c_mw * 256;
 	uint64_t nb = ((uint64_t)(ql + 63) / 64) * 64 * zrow + (uint64_t)WTZ_TRACE_MAXCHUNK * 8 + (uint64_t)(ql + 2) * 4 + 256;
@@ -1564,11 +1512,10 @@ static int run_stitch_fused(wtz_ctx *c, const wtz_env_t &V, const wtz_alnitem_t 
 	 * key = the rows both jobs can run at most, inverted (ascending stable radix sort = longest first, ties in item order); the trace bounds are summed with an atomic */
 	uint64_t *d_k = NULL; uint32_t *d_order = NULL; unsigned long long *d_acc = NULL;
 	uint32_t *d_open = NULL;
-	CHK(dev_alloc((void**)&d_k, (size_t)m * 8)); CHK(dev_alloc((void**)&d_order, (size_t)m * 4)); CHK(dev_alloc((void**)&d_acc, 32)); CHK(dev_set(d_acc, 0, 32));
+	CHK(dev_alloc((void**)&d_k, (size_t)m * 8)); CHK(dev_alloc((void**)&d_order, (size_t)m * 4)); CHK(dev_alloc((void**)&d_acc, 24)); CHK(dev_set(d_acc, 0, 24));
 	if(c->env_ext_pk) CHK(dev_alloc((void**)&d_open, ((size_t)m + 1) * 4));
 	{
 		const int32_t pM = c->P.M, pO = c->P.O, pE = c->P.E, pT = c->P.T, pW = -c->P.ew;
-		const uint32_t mw_rows = c->env_ext_mw_rows > 0 ? (uint32_t)c->env_ext_mw_rows : 0xFFFFFFFFu;
 		const bool use_pk = c->env_ext_pk != 0; const wtz_params_t *dP = V.P;
 		CHK(wtz_launch<K_misc>(0, m, [=] WTZ_LAMBDA (uint64_t t){
 			const wtz_extjob_t &j = d_jl[t];
@@ -1599,14 +1546,13 @@ static int run_stitch_fused(wtz_ctx *c, const wtz_env_t &V, const wtz_alnitem_t 
 				}
 			}
 			d_k[t] = ((uint64_t)to_fr << 32) | (uint64_t)(0xFFFFFFFFu - rows); d_order[t] = (uint32_t)t;
-			if(to_fr) WTZ_ATOMIC_ADD64(&d_acc[3], 1ull);
+			if(to_fr) WTZ_ATOMIC_ADD64(&d_acc[2], 1ull);
 			if(nb) WTZ_ATOMIC_ADD64(&d_acc[0], nb);
 			if(rows) WTZ_ATOMIC_ADD64(&d_acc[1], (unsigned long long)rows);
-			if(rows >= mw_rows) WTZ_ATOMIC_ADD64(&d_acc[2], 1ull);
 		}));
 	}
 	CHK(dev_sort_pairs_u64_u32(d_k, d_order, m, 33));
-	unsigned long long h_acc[4] = {0, 0, 0, 0}; CHK(dev_d2h(h_acc, d_acc, 32));
+	unsigned long long h_acc[3] = {0, 0, 0}; CHK(dev_d2h(h_acc, d_acc, 24));
 	const uint64_t acc = h_acc[0]; const unsigned long long ext_sum = h_acc[1];
 	const uint64_t budget = (c->pool_bytes - c->main_bytes) / 16 * 15;
 	/* acc sums UPPER bounds (every job run to its last row); the traces are allocated 64 rows at a time as a job runs, and most jobs end early: what the launches
@@ -1621,42 +1567,30 @@ static int run_stitch_fused(wtz_ctx *c, const wtz_env_t &V, const wtz_alnitem_t 
 		if(mg == 0) continue;
 		CHK(tpool_reset(c));
 		wtz_timer te; te.start();
-		/* the items at the head of the order (longest first) whose extensions can run >= WTZ_EXT_MW_ROWS rows: four wavefronts each on the side stream, beside the
-		 * one-wavefront launch over the rest - they are the launch's critical path (a row takes a wavefront ~2 us whatever else the device does) */
-		uint32_t n_long = 0;
-		if(ng == 1 && c->env_ext_mw_rows > 0){ n_long = (uint32_t)h_acc[2]; if(n_long > m / 8u) n_long = m / 8u; }
-		if(n_long){
-			HIPCHK(hipEventRecord(c->ev_mw_fork, g_stream)); HIPCHK(hipStreamWaitEvent(c->stream_mw, c->ev_mw_fork, 0));
-			hipLaunchKernelGGL((wtz_kernel_stitch_ext_frmw<1032>), dim3(n_long), dim3(256), WTZ_WAVE_LDS_BYTES, c->stream_mw, V, d_items, d_st, d_jl, d_jr, d_gaps, (const uint32_t*)d_order, n_long);
-			HIPCHK(hipGetLastError());
-			HIPCHK(hipEventRecord(c->ev_mw_join, c->stream_mw));
-		}
-		if(mg > n_long && c->env_ext_pk){
+		if(c->env_ext_pk){
 			/* the packed 16-bit form; the items dealt to the 32-bit form beforehand (the tail of the order: a handful of the longest extensions per step) run beside
 			 * it on the side stream; what the packed form declines after all is listed and finished by the 32-bit form behind it */
-			uint32_t n_fr = (ng == 1 && !n_long) ? (uint32_t)h_acc[3] : 0u;
-			if(n_fr > mg - n_long) n_fr = mg - n_long;
+			uint32_t n_fr = ng == 1 ? (uint32_t)h_acc[2] : 0u;
+			if(n_fr > mg) n_fr = mg;
 			CHK(dev_set(d_open, 0, 4));
 			if(n_fr){
-				HIPCHK(hipEventRecord(c->ev_mw_fork, g_stream)); HIPCHK(hipStreamWaitEvent(c->stream_mw, c->ev_mw_fork, 0));
-				hipLaunchKernelGGL((wtz_kernel_stitch_ext_fr<1032>), dim3(n_fr), dim3(64), WTZ_WAVE_LDS_BYTES, c->stream_mw, V, d_items, d_st, d_jl, d_jr, d_gaps, (const uint32_t*)d_order + (mg - n_fr), n_fr, 1u, 0u);
+				HIPCHK(hipEventRecord(c->ev_side_fork, g_stream)); HIPCHK(hipStreamWaitEvent(c->stream_side, c->ev_side_fork, 0));
+				hipLaunchKernelGGL((wtz_kernel_stitch_ext_fr<1032>), dim3(n_fr), dim3(64), WTZ_WAVE_LDS_BYTES, c->stream_side, V, d_items, d_st, d_jl, d_jr, d_gaps, (const uint32_t*)d_order + (mg - n_fr), n_fr, 1u, 0u);
 				HIPCHK(hipGetLastError());
-				HIPCHK(hipEventRecord(c->ev_mw_join, c->stream_mw));
+				HIPCHK(hipEventRecord(c->ev_side_join, c->stream_side));
 			}
-			const uint32_t n_pk = mg - n_long - n_fr;
+			const uint32_t n_pk = mg - n_fr;
 			if(n_pk){
-				hipLaunchKernelGGL((wtz_kernel_stitch_ext_pk<1032>), dim3(n_pk), dim3(64), WTZ_PK_LDS_BYTES(1032), g_stream, V, d_items, d_st, d_jl, d_jr, d_gaps, (const uint32_t*)d_order + n_long, n_pk, ng, g, d_open);
+				hipLaunchKernelGGL((wtz_kernel_stitch_ext_pk<1032>), dim3(n_pk), dim3(64), WTZ_PK_LDS_BYTES(1032), g_stream, V, d_items, d_st, d_jl, d_jr, d_gaps, (const uint32_t*)d_order, n_pk, ng, g, d_open);
 				HIPCHK(hipGetLastError());
 			}
-			if(n_fr) HIPCHK(hipStreamWaitEvent(g_stream, c->ev_mw_join, 0));
+			if(n_fr) HIPCHK(hipStreamWaitEvent(g_stream, c->ev_side_join, 0));
 			uint32_t n_open = 0; CHK(dev_d2h(&n_open, d_open, 4));
 			c->ext_open_total += n_open; c->ext_fr_total += n_fr;
 			if(n_open){ hipLaunchKernelGGL((wtz_kernel_stitch_ext_fr<1032>), dim3(n_open), dim3(64), WTZ_WAVE_LDS_BYTES, g_stream, V, d_items, d_st, d_jl, d_jr, d_gaps, (const uint32_t*)d_open + 1, n_open, 1u, 0u); HIPCHK(hipGetLastError()); }
-		} else if(mg > n_long) hipLaunchKernelGGL((wtz_kernel_stitch_ext_fr<1032>), dim3(mg - n_long), dim3(64), WTZ_WAVE_LDS_BYTES, g_stream, V, d_items, d_st, d_jl, d_jr, d_gaps, (const uint32_t*)d_order + n_long, mg - n_long, ng, g);
+		} else hipLaunchKernelGGL((wtz_kernel_stitch_ext_fr<1032>), dim3(mg), dim3(64), WTZ_WAVE_LDS_BYTES, g_stream, V, d_items, d_st, d_jl, d_jr, d_gaps, (const uint32_t*)d_order, mg, ng, g);
 		HIPCHK(hipGetLastError());
-		if(n_long) HIPCHK(hipStreamWaitEvent(g_stream, c->ev_mw_join, 0));
 		ms_l += te.stop();
-		if(c->env_profile && n_long) fprintf(stderr, "[ext-profile] %u of %u items on four wavefronts each\n", n_long, m);
 		{
 			const int rc_t = tpool_check(c, "K-sw3 extension jobs (both ends on one wavefront)");
 			if(rc_t != WTZ_OK){
@@ -1744,7 +1678,6 @@ static int run_extjobs(wtz_ctx *c, const wtz_env_t &V, wtz_extjob_t *d_jobs, uin
 	}
 	{
 		wtz_timer te; te.start();
-		const int use_reg = c->env_use_reg;
 		/* launch groups: consecutive jobs of the order whose trace upper bounds fit the transient pool together; the pool is reset
 		 * between groups (the CIGARs went to the main pool).  One group is the normal case. */
 		const uint64_t budget = (c->pool_bytes - c->main_bytes) / 16 * 15;
@@ -1753,19 +1686,15 @@ static int run_extjobs(wtz_ctx *c, const wtz_env_t &V, wtz_extjob_t *d_jobs, uin
 			uint32_t g1 = g0; uint64_t acc = 0;
 			while(g1 < m && (g1 == g0 || acc + need[ord[g1]] <= budget)){ acc += need[ord[g1]]; g1++; }
 			CHK(tpool_reset(c));      /* the traces of the previous group / the previous stage are dead: their CIGARs are in the main pool */
-			if(use_reg){
-				/* one wavefront per job, longest first: the frame form (wtz_sw_frame.h), or the round-4 register form it replaced (WTZ_EXT_FR=0: kept as DP form 1, the
-				 * reference the isolated bench compares against).  Retired in round 6 (git history keeps them): the launches per band class (WTZ_EXT_SPLIT, WTZ_EXT_FR_SPLIT:
-				 * profiles/r06_ksw3_split_in_step_kernel_trace.txt) and the round-4 four-wave kernel with its WTZ_SW_MW_MIN / WTZ_EXT_MW_CW routing. */
-				if(c->env_ext_fr && c->env_ext_pk){      /* two 16-bit cells per register (wtz_sw_frame16.h); what is outside its window stays open for the 32-bit form */
-					hipLaunchKernelGGL((wtz_kernel_extjobs_pk<1032>), dim3(g1 - g0), dim3(64), 0, g_stream, d_jobs, (const uint32_t*)d_order + g0, g1 - g0, V.P, V.pool, V.pool + 1);
-					HIPCHK(hipGetLastError());
-				}
-				if(c->env_ext_fr) hipLaunchKernelGGL((wtz_kernel_extjobs_fr<1032>), dim3(g1 - g0), dim3(64), 0, g_stream, d_jobs, (const uint32_t*)d_order + g0, g1 - g0, V.P, V.pool, V.pool + 1);
-				else hipLaunchKernelGGL((wtz_kernel_extjobs_reg<1032>), dim3(g1 - g0), dim3(64), 0, g_stream, d_jobs, (const uint32_t*)d_order + g0, g1 - g0, V.P, V.pool, V.pool + 1);
+			/* one wavefront per job, longest first: the packed form, the 32-bit frame form (wtz_sw_frame.h) for what is outside the packed form's window, the
+			 * general kernel for what is outside the frame forms' envelope.  The forms these replaced are in the git history; CHANGELOG.md has their numbers. */
+			if(c->env_ext_pk){      /* two 16-bit cells per register (wtz_sw_frame16.h); what is outside its window stays open for the 32-bit form */
+				hipLaunchKernelGGL((wtz_kernel_extjobs_pk<1032>), dim3(g1 - g0), dim3(64), 0, g_stream, d_jobs, (const uint32_t*)d_order + g0, g1 - g0, V.P, V.pool, V.pool + 1);
 				HIPCHK(hipGetLastError());
 			}
-			hipLaunchKernelGGL((wtz_kernel_extjobs<2048, 1032>), dim3(g1 - g0), dim3(64), 0, g_stream, d_jobs, (const uint32_t*)d_order + g0, g1 - g0, V.P, V.pool, V.pool + 1);     /* whatever the register DP left */
+			hipLaunchKernelGGL((wtz_kernel_extjobs_fr<1032>), dim3(g1 - g0), dim3(64), 0, g_stream, d_jobs, (const uint32_t*)d_order + g0, g1 - g0, V.P, V.pool, V.pool + 1);
+			HIPCHK(hipGetLastError());
+			hipLaunchKernelGGL((wtz_kernel_extjobs<2048, 1032>), dim3(g1 - g0), dim3(64), 0, g_stream, d_jobs, (const uint32_t*)d_order + g0, g1 - g0, V.P, V.pool, V.pool + 1);     /* whatever the frame forms left */
 			HIPCHK(hipGetLastError());
 			if(g1 < m || n_groups){ CHK(dev_sync()); CHK(tpool_check(c, "K-sw3 extension jobs")); }
 			g0 = g1; n_groups++;
@@ -1779,7 +1708,7 @@ static int run_extjobs(wtz_ctx *c, const wtz_env_t &V, wtz_extjob_t *d_jobs, uin
 			{ std::vector<wtz_extjob_t> jj(m); CHK(dev_d2h(jj.data(), d_jobs, (size_t)m * sizeof(wtz_extjob_t))); uint32_t nd[4] = {0, 0, 0, 0}; for(uint32_t i = 0; i < m; i++){ key[i] = jj[i].valid ? jj[i].x.qe : -1; if(jj[i].valid) nd[jj[i].done & 3]++; }
 			  if(const char *dp = getenv("WTZ_EXT_DUMP")){      /* job geometry of this call, 8 int32 per valid job: the input of tools/ubench/ksw3_bench.py */
 				if(FILE *df = fopen(dp, "ab")){ for(uint32_t i = 0; i < m; i++) if(jj[i].valid){ const int32_t r[8] = {jj[i].qlen, jj[i].tlen, jj[i].init_score, jj[i].W, jj[i].x.qe, jj[i].x.te, (int32_t)(jj[i].cells > 0x7FFFFFFFull ? 0x7FFFFFFF : jj[i].cells), (int32_t)jj[i].done}; fwrite(r, 4, 8, df); } fclose(df); } }
-			  fprintf(stderr, "[ext-profile] %u launch group(s); valid jobs finished by: nobody %u, one-wave %u, four-wave %u, general %u\n", n_groups, nd[0], nd[1], nd[2], nd[3]); }
+			  fprintf(stderr, "[ext-profile] %u launch group(s); valid jobs finished by: nobody %u, 32-bit frame form %u, packed form or general kernel %u\n", n_groups, nd[0], nd[1], nd[3]); }
 			for(uint32_t i = 0; i < m; i++){ if(key[i] < 0) continue; nv++; if(key[i] >= 256) n256++; if(key[i] >= 512){ n512++; s512 += key[i]; } if(key[i] >= 1024) n1k++; if(key[i] >= 2048) n2k++; if(key[i] >= 4096) n4k++; }
 			fprintf(stderr, "[ext-profile] %u jobs (%u valid), rows (upper bound) sum %llu max %d, %.2f ms; qe>=256 %u >=512 %u (sum %llu) >=1k %u >=2k %u >=4k %u; transient pool peak %.2f GB\n", m, nv, ext_sum, ext_max, ms_l, n256, n512, s512, n1k, n2k, n4k, c->tpool_peak_call / 1073741824.0);
 		}
@@ -1976,7 +1905,7 @@ extern "C" int wtz_pairs_align(wtz_ctx_t *c, const uint32_t *pair_idx, const uin
 	lapw(0);
 	wtz_timer tm; tm.start();
 	bool lane_done = false;
-	if(c->env_lane && !c->env_grp4){
+	if(c->env_lane){
 		/* one lane per K-sw1 problem (wtz_sw_lane.h); what it leaves (d_fb) goes through the chained kernel below */
 		const uint64_t nwt0 = (size_t)nreg;
 		uint32_t *d_fb = NULL, n_fb = 0;
@@ -2002,26 +1931,17 @@ extern "C" int wtz_pairs_align(wtz_ctx_t *c, const uint32_t *pair_idx, const uin
 	if(!lane_done) CHK(wtz_launch_coop<K_winalign>(0, (size_t)nreg, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_winalign((uint32_t)t, V, d_wt, d_items); }, WTZ_WINALIGN_LDS_BYTES + WTZ_WINALIGN_QW_BYTES));
 #else
 	if(!lane_done){
-		/* first launch: FOUR windows per wavefront (one per 16-lane group, wtz_sw_grp.h); a window with a problem outside the group form's
-		 * envelope queues itself for the one-window-per-wave kernel: its lean form first (register DP with one / two band columns per lane,
-		 * no scalar body: fewer VGPRs), then - for what that form defers in turn - the full task */
+		/* one window per wavefront: the lean form of the chained kernel first (register DP with one / two band columns per lane, no scalar
+		 * body: fewer VGPRs); a window with a problem outside its envelope queues itself for the full task */
 		const uint64_t nwt0 = (size_t)nreg;
-		uint32_t *d_defer4 = NULL, *d_defer = NULL;
-		CHK(dev_alloc((void**)&d_defer4, (nwt0 + 1) * 4)); CHK(dev_set(d_defer4, 0, 4));
+		uint32_t *d_defer = NULL;
 		CHK(dev_alloc((void**)&d_defer, (nwt0 + 1) * 4)); CHK(dev_set(d_defer, 0, 4));
 		STAGE(c, "K_winalign");
-		uint32_t n_def4 = 0, n_def = 0;
-		if(c->env_grp4){
-			CHK(wtz_launch_grp<K_winalign4>(nwt0, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_winalign4((uint32_t)t, (uint32_t)nwt0, V, d_wt, d_items, d_defer4); }, WTZ_WINALIGN4_LDS_BYTES));
-			CHK(dev_d2h(&n_def4, d_defer4, 4));
-			if(n_def4) CHK(wtz_launch_coop<K_winalign>(0, n_def4, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_winalign<false>((uint32_t)t, V, d_wt, d_items, d_defer, d_defer4); }, WTZ_WINALIGN_LDS_BYTES + WTZ_WINALIGN_QW_BYTES));
-		} else {
-			CHK(wtz_launch_coop<K_winalign>(0, nwt0, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_winalign<false>((uint32_t)t, V, d_wt, d_items, d_defer, NULL); }, WTZ_WINALIGN_LDS_BYTES + WTZ_WINALIGN_QW_BYTES));
-		}
+		uint32_t n_def = 0;
+		CHK(wtz_launch_coop<K_winalign>(0, nwt0, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_winalign<false>((uint32_t)t, V, d_wt, d_items, d_defer, NULL); }, WTZ_WINALIGN_LDS_BYTES + WTZ_WINALIGN_QW_BYTES));
 		CHK(dev_d2h(&n_def, d_defer, 4));
 		if(n_def) CHK(wtz_launch_coop<K_winalign_big>(0, n_def, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_winalign<true>((uint32_t)t, V, d_wt, d_items, NULL, d_defer); }, WTZ_WINALIGN_LDS_BYTES + WTZ_WINALIGN_QW_BYTES));
-		if(c->env_profile) fprintf(stderr, "[winalign-profile] %zu windows, %u left by the four-per-wave form, %u redone by the full task\n", (size_t)nreg, n_def4, n_def);
-		dev_free(d_defer4);
+		if(c->env_profile) fprintf(stderr, "[winalign-profile] %zu windows, %u redone by the full task\n", (size_t)nreg, n_def);
 		dev_free(d_defer);
 	}
 #endif
@@ -2056,7 +1976,7 @@ extern "C" int wtz_pairs_align(wtz_ctx_t *c, const uint32_t *pair_idx, const uin
 		STAGE(c, "K_stitch_left");
 		int32_t *d_rgeo = NULL;
 #ifndef WTZ_EMUL
-		const bool fused = c->env_ext_fused && c->env_ext_fr && c->env_sw_mode == 0 && c->env_use_reg;
+		const bool fused = c->env_ext_fused && c->env_sw_mode == 0;
 		if(fused) CHK(dev_alloc((void**)&d_rgeo, (size_t)m * 8));
 #else
 		CHK(dev_alloc((void**)&d_rgeo, (size_t)m * 8));      /* host emulation: the prediction of the right extension's geometry is compared with what K_stitch_mid asks for */
@@ -2258,7 +2178,7 @@ extern "C" int wtz_cigar_text_device(wtz_ctx_t *c, uint64_t n_bytes, void **dev_
 /* f2: end extensions for a caller that holds its own overlaps (wtext)                                */
 /* ------------------------------------------------------------------------------------------------ */
 /* kswx_extend_align (kswx.h:469-481) = kswx_extend_align_shift_core (kswx.h:101-232) for n independent problems on views of the uploaded reads: the SAME job
- * dispatch as the ends of wtzmo's stitched alignments (run_extjobs: register DP on one or four wavefronts per job, LDS-ring and scalar forms for what is
+ * dispatch as the ends of wtzmo's stitched alignments (run_extjobs: register DP on one wavefront per job, LDS-ring and scalar forms for what is
  * outside their envelope).  out[i]: the kswx_t of the call + where its CIGAR words (traceback order reversed: first operation first) start in `cigar`. */
 struct K_extcopy;
 extern "C" int wtz_extend_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32_t n, wtz_dp_result_t *out, uint32_t *cigar, uint64_t cigar_cap){

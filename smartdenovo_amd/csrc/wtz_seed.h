@@ -523,151 +523,6 @@ WTZ_HD void wtz_coop_sort_u32(uint32_t *w, uint32_t np){
 #endif
 }
 
-#define WTZ_CAND_SKETCH 2048u
-#define WTZ_CAND_TAB 2048u
-#define WTZ_CAND_OUT 512u
-#define WTZ_CAND_STREAM_LDS_BYTES(ncand) ((WTZ_CAND_SKETCH + 3u * WTZ_CAND_TAB) * 4u + WTZ_CAND_OUT * 8u + ((ncand) + 2u) * 8u)
-#if defined(__HIP_DEVICE_COMPILE__)
-/*
- * Phases C-E of the candidate task without expanding and sorting the tuples.
- *
- * The reference's k-way merge (wtzmo.c:500-560) delivers the tuples of one (read, strand) group in query-offset order and folds them with
- *     ol += (qoff >= lst) ? len : qoff + len - lst;   lst = qoff + len            (u32; a later, shorter k-mer moves lst back)
- * and only groups with ol >= -d (kovl) ever matter (wtzmo.c:523).  Two facts make a sort-free form exact:
- *   (1) by induction ol >= len of the last tuple > 0 and every step adds at most len, so 0 < ol <= SUM(len): a group whose lengths sum to
- *       less than kovl can be dropped without looking at its order.  Most groups of a query are such chance hits of erroneous k-mers
- *       (~1 500 groups per 10 kb query, ~200 of them real) - a table of ALL groups does not fit LDS, a table of the survivors does;
- *   (2) the sampled k-mers of the query are listed in query-offset order and the seed run of one k-mer is sorted by (read, strand): walking
- *       the k-mers in order with the lanes side by side on the entries of a run gives every group its tuples in the reference's order.
- * Pass 1 (order-free, every lane its own k-mers): LDS sketch  S[hash(read,strand)] += len.  Pass 2 (64 k-mers at a time, every lane its own):
- * does the run have an entry with S >= kovl?  Pass 3 (those k-mers only, in order, 8 runs in flight): fold the surviving entries into an
- * LDS hash table of (lst, ol).  Then the groups with ol >= kovl are compacted, put in (read, strand) order and lane 0 replays the strand merge and
- * the candidate heap (staged in LDS).  Returns false (nothing written) when the survivors overflow the table: the caller then runs the
- * sorting form.
- * id_thr: when the indexed reads are in non-increasing length order (always, unless -b clipped them after the sort) "longer than 1.2 x
- * the query" (wtzmo.c:489) is "read id below id_thr" - no length load per run entry; 0xFFFFFFFF = look the length up.
- */
-WTZ_D bool wtz_cand_stream(uint32_t t, const wtz_reads_t &R, uint32_t pbid, uint32_t pblen_up, const wtz_params_t *P, const uint32_t *seeds,
-		uint32_t nk, const uint64_t *koff, const uint32_t *kqoff, const uint32_t *kqlen, uint64_t *cand_out, uint32_t *ncand_out, uint32_t stride, uint32_t *lds32, uint32_t id_thr){
-	const uint32_t lane = WTZ_LANE, EMPTY = 0xFFFFFFFFu, MASK = WTZ_CAND_TAB - 1u, SMASK = WTZ_CAND_SKETCH - 1u;
-	uint32_t *sk = lds32, *keys = sk + WTZ_CAND_SKETCH, *lsts = keys + WTZ_CAND_TAB, *ols = lsts + WTZ_CAND_TAB;
-	uint64_t *out = (uint64_t*)(ols + WTZ_CAND_TAB), *heap = out + WTZ_CAND_OUT;
-	const uint32_t kovl = P->kovl;
-	if(P->ncand + 1u > 1024u) return false;
-	for(uint32_t i = lane; i < WTZ_CAND_SKETCH; i += 64) sk[i] = 0u;
-	for(uint32_t i = lane; i < WTZ_CAND_TAB; i += 64) keys[i] = EMPTY;
-	__threadfence_block();
-	auto dropped = [&](uint32_t sd) -> bool {                                  /* wtzmo.c:488-489 */
-		if((sd >> 1) == pbid) return true;
-		if(id_thr != 0xFFFFFFFFu) return (sd >> 1) < id_thr;
-		return R.rdlen[sd >> 1] > pblen_up;
-	};
-	/* ---- pass 1: length sums per (read, strand) hash ---- */
-	for(uint32_t e = lane; e < nk; e += 64){
-		const uint64_t oc = koff[e]; const uint32_t c = (uint32_t)(oc & 0xFFFFu); const uint64_t o = oc >> 16;
-		const uint32_t ql = kqlen[e] < kovl ? kqlen[e] : kovl;                 /* clamped: the sums cannot wrap */
-		uint32_t prev = EMPTY;
-		for(uint32_t k = 0; k < c; k++){
-			const uint32_t sd = seeds[o + k];
-			if(sd != prev && !dropped(sd)) atomicAdd(&sk[(uint32_t)wtz_mix64(sd) & SMASK], ql);       /* an identical neighbour adds 0 to ol */
-			prev = sd;
-		}
-	}
-	__threadfence_block();
-	uint32_t ngrp = 0;
-	/* one run entry per lane: group lookup / insert and the fold of this k-mer's interval */
-	auto fold = [&](uint32_t sd, uint32_t prev, bool in_run, uint32_t qo, uint32_t ql){
-		bool act = in_run && sd != prev && !dropped(sd) && sk[(uint32_t)wtz_mix64(sd) & SMASK] >= kovl;
-		bool fresh = false;
-		if(act){
-			uint32_t h = (uint32_t)wtz_mix64(sd * 0x9E3779B1u) & MASK;
-			for(;;){
-				const uint32_t old = atomicCAS(&keys[h], EMPTY, sd);
-				if(old == EMPTY){ fresh = true; break; }
-				if(old == sd) break;
-				h = (h + 1u) & MASK;
-			}
-			uint32_t lst = fresh ? 0u : lsts[h], ol = fresh ? 0u : ols[h];
-			if(qo >= lst) ol += ql; else ol += qo + ql - lst;                     /* wtzmo.c:558-559 */
-			lsts[h] = qo + ql; ols[h] = ol;
-		}
-		ngrp += (uint32_t)__popcll(__ballot(fresh));
-		__threadfence_block();
-	};
-	/* ---- pass 3 ---- */
-	constexpr int PF = 8;                                /* runs whose first 64 entries are in flight together: the walk is a chain of dependent loads otherwise */
-	for(uint32_t e0 = 0; e0 < nk; e0 += 64){
-		const uint32_t e = e0 + lane;
-		const uint64_t oc = e < nk ? koff[e] : 0ull;
-		uint32_t my_c = (uint32_t)(oc & 0xFFFFu); const uint32_t my_olo = (uint32_t)(oc >> 16), my_ohi = (uint32_t)(oc >> 48);
-		const uint32_t my_q = e < nk ? kqoff[e] : 0u, my_l = e < nk ? kqlen[e] : 0u;
-		{   /* pass 2, every lane its own k-mer: a run without an entry that can reach -d is not walked */
-			bool any = false;
-			for(uint32_t k = 0; k < my_c && !any; k++){ const uint32_t sd = seeds[(oc >> 16) + k]; if(!dropped(sd) && sk[(uint32_t)wtz_mix64(sd) & SMASK] >= kovl) any = true; }
-			if(!any) my_c = 0;
-		}
-		unsigned long long hits = __ballot(my_c != 0);
-		while(hits){
-			int ls[PF]; uint32_t cs[PF], sdv[PF]; uint64_t os[PF];
-			#pragma unroll
-			for(int g = 0; g < PF; g++){
-				ls[g] = -1; cs[g] = 0; os[g] = 0; sdv[g] = EMPTY;
-				if(hits){
-					const int l = __builtin_ctzll(hits); hits &= hits - 1ull; ls[g] = l;
-					cs[g] = (uint32_t)__builtin_amdgcn_readlane((int)my_c, l);
-					os[g] = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)my_ohi, l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)my_olo, l);
-					if(lane < cs[g]) sdv[g] = seeds[os[g] + lane];
-				}
-			}
-			#pragma unroll
-			for(int g = 0; g < PF; g++){
-				if(ls[g] < 0) continue;                      /* uniform */
-				const uint32_t c = cs[g], qo = (uint32_t)__builtin_amdgcn_readlane((int)my_q, ls[g]), ql = (uint32_t)__builtin_amdgcn_readlane((int)my_l, ls[g]);
-				if(ngrp + 64u > WTZ_CAND_TAB - WTZ_CAND_TAB / 4u){ WTZ_PROF_CNT(46, 1000000); return false; }      /* more survivors than the table takes at load 3/4 */
-				uint32_t sd = sdv[g];
-				uint32_t prev = (uint32_t)__shfl_up((int)sd, 1, 64); if(lane == 0) prev = EMPTY;
-				uint32_t carry = (uint32_t)__builtin_amdgcn_readlane((int)sd, 63);       /* last entry of the previous 64 of this run */
-				fold(sd, prev, lane < c, qo, ql);
-				for(uint32_t k0 = 64; k0 < c; k0 += 64){
-					if(ngrp + 64u > WTZ_CAND_TAB - WTZ_CAND_TAB / 4u){ WTZ_PROF_CNT(46, 1000000); return false; }
-					const uint32_t k = k0 + lane;
-					sd = k < c ? seeds[os[g] + k] : EMPTY;
-					prev = (uint32_t)__shfl_up((int)sd, 1, 64); if(lane == 0) prev = carry;
-					carry = (uint32_t)__builtin_amdgcn_readlane((int)sd, 63);
-					fold(sd, prev, k < c, qo, ql);
-				}
-			}
-		}
-	}
-	/* groups that reach -d, in (read, strand) order */
-	uint32_t ng = 0;
-	for(uint32_t i0 = 0; i0 < WTZ_CAND_TAB; i0 += 64){
-		const uint32_t i = i0 + lane;
-		const bool keep = keys[i] != EMPTY && ols[i] >= kovl;
-		uint32_t tot; const uint32_t pos = wtz_coop_rank(keep, &tot);
-		if(ng + tot > WTZ_CAND_OUT){ WTZ_PROF_CNT(47, 1000000); return false; }
-		if(keep) out[ng + pos] = ((uint64_t)keys[i] << 32) | ols[i];
-		ng += tot;
-	}
-	uint32_t np = 64; while(np < ng) np <<= 1;
-	for(uint32_t i = ng + lane; i < np; i += 64) out[i] = ~0ull;
-	__threadfence_block();
-	wtz_coop_sort_u64(out, np);
-	/* strand merge + candidate heap with its quirks (wtzmo.c:516-571) on lane 0, the heap row staged in LDS */
-	uint32_t hn = ncand_out[t];
-	uint64_t *row = cand_out + (size_t)t * stride;
-	for(uint32_t i = lane; i < hn; i += 64) heap[i] = row[i];
-	__threadfence_block();
-	if(lane == 0) wtz_cand_tail(out, ng, kovl, P->ncand, heap, &hn);
-	hn = wtz_coop_bcast32(hn);
-	__threadfence_block();
-	for(uint32_t i = lane; i < hn; i += 64) row[i] = heap[i];
-	if(lane == 0) ncand_out[t] = hn;
-	WTZ_PROF_CNT(10, 1000000); WTZ_PROF_CNT(11, ngrp * 1000ull); WTZ_PROF_CNT(12, ng * 1000ull);
-	return true;
-}
-#endif
-
 /* ================= K-seed, workgroup form: partition by target read, sort each bucket in LDS =================
  *
  * What the numbers of configs[2] say (tools/analysis/seedstats.c, 100x coverage of a 12 Mbp genome): a query of 15-50 kb has 3-10 k sampled
@@ -675,7 +530,7 @@ WTZ_D bool wtz_cand_stream(uint32_t t, const wtz_reads_t &R, uint32_t pbid, uint
  * hp-compressed 16-mers of a 12 Mbp genome collide by chance, so nearly every group is a chance hit of one or two k-mers.  One wavefront
  * per query ordered all tuples with a bitonic network through a 16 KB LDS window: ~700 bytes of HBM traffic per 4-byte seed entry (PMC:
  * 830 GB per step against 5 GB algorithmic), 0.1 % of the HBM roof.  No LDS table can hold 100 k groups, and a sketch in front of it
- * saturates at that density (the streaming form above fell back for a third of the long queries).
+ * saturates at that density (a sort-free streaming form built on one fell back for a third of the long queries; it and the one-wavefront sorting form were removed, see CHANGELOG.md).
  *
  * This form moves every tuple through HBM exactly once, as an MSD radix step by target read:
  *   A  the workgroup's threads walk one piece of the read each and list its sampled k-mers (exact restart: wtz_walk_warm_start)
@@ -1347,149 +1202,6 @@ WTZ_HD void wtz_task_candidates_wg(uint32_t t, wtz_reads_t R, const uint32_t *qi
 		wtz_cand_tail(grp, ng, kovl, P->ncand, cand_out + (size_t)t * stride, &hn);
 		ncand_out[t] = hn;
 	}
-}
-
-struct wtz_kq_f { uint64_t *mer; uint32_t *qoff, *qlen; uint32_t n;
-	WTZ_HDM void operator()(uint64_t m, uint32_t, uint32_t qo, uint32_t qe){ uint32_t l = qe - qo; if(l > 0xFFFFu) l = 0xFFFFu; mer[n] = m; qoff[n] = qo; qlen[n] = l; n++; } };
-
-/*
- * task (wave-cooperative): candidates of query qids[t]; cand_out row stride = ncand + 1.
- *   A  lane 0 walks the read once and lists its sampled k-mers (the hp-compressed walk is a serial recurrence)
- *   B  all lanes probe the hash (one 16-byte slot load per k-mer) and lay out the seed runs with an exclusive scan
- *   C  all lanes expand (read<<1|strand, query offset, length) tuples, dropping self hits and reads longer than 1.2x
- *      (wtzmo.c:488-489); tuple sequence numbers follow query-offset order
- *   D  wave-wide bitonic sort of (key<<32 | sequence): per (read,strand) group the tuples stay in query-offset order,
- *      which is the order the reference's k-way heap merge delivers them in (wtzmo.c:44-57)
- *   E  all lanes: group heads -> union length `ol` of each group (wtzmo.c:558-560), compacted in key order
- *   F  lane 0 replays the strand merge + candidate heap with its quirks (wtzmo.c:516-571)
- */
-template<bool STREAM = false>
-WTZ_HD void wtz_task_candidates(uint32_t t, wtz_reads_t R, const uint32_t *qids, const wtz_params_t *P,
-		const wtz_kslot_t *tab, uint64_t tmask, const uint32_t *seeds, wtz_pool_t *pool, uint64_t *cand_out, uint32_t *ncand_out, uint32_t stride,
-		unsigned long long *algo_bytes, uint64_t *lds, uint32_t lds_words, const uint32_t *id_thr = NULL){
-	const uint32_t pbid = qids[t], lane = WTZ_LANE;
-	const uint32_t L = R.rdlen[pbid];
-	const uint32_t pblen_up = (uint32_t)(L * 1.2);                       /* double multiply, wtzmo.c:445 */
-	/* ---- A ---- */
-	const unsigned long long pcA = WTZ_PROF_T(); (void)pcA;
-	uint64_t pa = 0; uint32_t nk = 0;
-	if(lane == 0) pa = (uint64_t)(uintptr_t)wtz_pool_alloc(pool, (size_t)(L + 2) * 16 + (size_t)(L + 2) * 12);
-	pa = wtz_coop_bcast64(pa);
-	if(pa == 0){ if(lane == 0) ncand_out[t] = 0xFFFFFFFFu; return; }
-	uint8_t *mem = (uint8_t*)(uintptr_t)pa;
-	{   /* every lane walks one piece of the read (exact restart: wtz_walk_warm_start), counts, then writes at its offset */
-		const uint32_t PL = (L + WTZ_NLANES - 1) / WTZ_NLANES;
-		const uint32_t jb = lane * PL, je = jb + PL;
-		uint32_t cnt = 0;
-		if(jb < L || (lane == 0 && L == 0)){ wtz_kcount_f fc; fc.n = 0; wtz_kmer_walk(R, pbid, P->ksize, P->hk, P->ksave, fc, jb, je); cnt = fc.n; }
-		uint32_t tot; const uint32_t ex = wtz_coop_excl_scan(cnt, &tot);
-		nk = tot;
-		if(cnt){
-			wtz_kq_f f; f.mer = (uint64_t*)mem; f.qoff = (uint32_t*)(mem + (size_t)(L + 2) * 8); f.qlen = f.qoff + (L + 2); f.n = ex;
-			wtz_kmer_walk(R, pbid, P->ksize, P->hk, P->ksave, f, jb, je);
-		}
-	}
-	WTZ_WAVE_SYNC();
-	const uint64_t *kmer = (const uint64_t*)mem; const uint32_t *kqoff = (const uint32_t*)(mem + (size_t)(L + 2) * 8), *kqlen = kqoff + (L + 2);
-	uint64_t *koff = (uint64_t*)(mem + (size_t)(L + 2) * 16);               /* seed run start per k-mer */
-	uint32_t *ktoff = (uint32_t*)(koff + (L + 2));                           /* tuple offset per k-mer (cnt kept in the high part of koff) */
-	WTZ_PROF_ADD(24, pcA);
-	const unsigned long long pcB = WTZ_PROF_T(); (void)pcB;
-	/* ---- B ---- */
-	uint32_t T = 0;
-	for(uint32_t e0 = 0; e0 < nk; e0 += WTZ_NLANES){
-		const uint32_t e = e0 + lane;
-		uint64_t o = 0; uint32_t c = 0;
-		if(e < nk){ if(!wtz_kprobe(tab, tmask, kmer[e], &o, &c)){ o = 0; c = 0; } }
-		uint32_t chunk; const uint32_t ex = wtz_coop_excl_scan(c, &chunk);
-		if(e < nk){ koff[e] = (o << 16) | c; ktoff[e] = T + ex; }
-		T += chunk;
-	}
-	if(lane == 0){
-		const unsigned long long bytes = (unsigned long long)L / 4 + 16ull * nk + 4ull * T;      /* SURVEY 8d */
-#if defined(__HIP_DEVICE_COMPILE__)
-		atomicAdd(algo_bytes, bytes);
-#else
-		*algo_bytes += bytes;
-#endif
-	}
-	WTZ_PROF_ADD(25, pcB); WTZ_PROF_CNT(30, T); WTZ_PROF_CNT(31, nk);
-	const unsigned long long pcC = WTZ_PROF_T(); (void)pcC;
-#if defined(__HIP_DEVICE_COMPILE__)
-	/* the streaming form (no tuples, no sort) when the launch gave the wave its table; a query with too many groups falls through.
-	 * A separate instantiation: the sorting form keeps its register budget (and occupancy) when the streaming form is not asked for */
-	if(STREAM && lds && lds_words * 8u >= WTZ_CAND_STREAM_LDS_BYTES(P->ncand)){
-		WTZ_WAVE_SYNC();
-		if(wtz_cand_stream(t, R, pbid, pblen_up, P, seeds, nk, koff, kqoff, kqlen, cand_out, ncand_out, stride, (uint32_t*)lds, id_thr ? id_thr[t] : 0xFFFFFFFFu)){ WTZ_PROF_ADD(26, pcC); return; }
-		WTZ_WAVE_SYNC();
-		/* the sorting form below wants a power-of-two LDS window, and wants it as a compile-time constant (constant strides in the
-		 * bitonic network): the sketch + table alone are 32 KB */
-		lds_words = (WTZ_CAND_SKETCH + 3u * WTZ_CAND_TAB) * 4u / 8u;
-	}
-#endif
-	/* ---- C ---- */
-	uint32_t np = 64; while(np < T) np <<= 1;
-	pa = 0;
-	if(lane == 0) pa = (uint64_t)(uintptr_t)wtz_pool_alloc(pool, (size_t)np * 8 + (size_t)(T + 2) * 8 + (size_t)(T + 2) * 8);
-	pa = wtz_coop_bcast64(pa);
-	if(pa == 0){ if(lane == 0) ncand_out[t] = 0xFFFFFFFFu; return; }
-	uint64_t *tup = (uint64_t*)(uintptr_t)pa, *tv = tup + np, *grp = tv + (T + 2);
-	for(uint32_t i = T + lane; i < np; i += WTZ_NLANES) tup[i] = ~0ull;
-#if defined(__HIP_DEVICE_COMPILE__)
-	__threadfence_block();
-#endif
-	for(uint32_t e = lane; e < nk; e += WTZ_NLANES){
-		const uint32_t c = (uint32_t)(koff[e] & 0xFFFFu); const uint64_t o = koff[e] >> 16;
-		const uint32_t base = ktoff[e];
-		const uint64_t v = ((uint64_t)kqoff[e] << 16) | kqlen[e];
-		for(uint32_t k = 0; k < c; k++){
-			const uint32_t sd = seeds[o + k];
-			const bool drop = ((sd >> 1) == pbid) || (R.rdlen[sd >> 1] > pblen_up);          /* wtzmo.c:488-489 */
-			tup[base + k] = drop ? ~0ull : (((uint64_t)sd << 32) | (base + k));
-			tv[base + k] = v;
-		}
-	}
-	WTZ_PROF_ADD(26, pcC);
-	const unsigned long long pcD = WTZ_PROF_T(); (void)pcD;
-	/* ---- D ---- */
-	wtz_coop_sort_u64_windowed(tup, np, lds, lds_words);
-	WTZ_PROF_ADD(27, pcD);
-	const unsigned long long pcE = WTZ_PROF_T(); (void)pcE;
-	/* ---- E ---- */
-	uint32_t ng = 0;
-	for(uint32_t i0 = 0; i0 < T; i0 += WTZ_NLANES){
-		const uint32_t i = i0 + lane;
-		uint32_t head = 0; uint64_t g = 0;
-		if(i < T && tup[i] != ~0ull){
-			const uint32_t key = (uint32_t)(tup[i] >> 32);
-			if(i == 0 || (uint32_t)(tup[i - 1] >> 32) != key){
-				head = 1;
-				uint32_t ol = 0, lst = 0;
-				for(uint32_t r = i; r < T && tup[r] != ~0ull && (uint32_t)(tup[r] >> 32) == key; r++){
-					const uint64_t v = tv[(uint32_t)tup[r]];
-					const uint32_t qo = (uint32_t)(v >> 16), ql = (uint32_t)(v & 0xFFFFu);
-					if(qo >= lst) ol += ql; else ol += qo + ql - lst;                           /* wtzmo.c:558-559 */
-					lst = qo + ql;
-				}
-				g = ((uint64_t)key << 32) | ol;
-			}
-		}
-		uint32_t chunk; const uint32_t ex = wtz_coop_excl_scan(head, &chunk);
-		if(head) grp[ng + ex] = g;
-		ng += chunk;
-	}
-#if defined(__HIP_DEVICE_COMPILE__)
-	__threadfence_block();
-#endif
-	WTZ_PROF_ADD(28, pcE);
-	const unsigned long long pcF = WTZ_PROF_T(); (void)pcF;
-	/* ---- F ---- */
-	if(lane == 0){
-		uint32_t hn = ncand_out[t];                 /* heap carried across index parts (-G), 0 otherwise */
-		wtz_cand_tail(grp, ng, P->kovl, P->ncand, cand_out + (size_t)t * stride, &hn);
-		ncand_out[t] = hn;
-	}
-	WTZ_PROF_ADD(29, pcF);
 }
 
 #endif

@@ -2,7 +2,8 @@
  * K-sw3 (kswx_extend_align_shift_core, /root/reference/kswx.h:101-232) on one wavefront, round-5 form: the DP runs in the
  * ANTI-DIAGONAL FRAME  G(i,j) = H(i,j) - (i+j)*E  (same for the E and F states).
  *
- * Why: wtz_extend_shift_reg (wtz_sw_wave.h) spends ~35 VALU ops per cell, a third of them on things that are not the recurrence:
+ * Why: the register kernel this form replaced (round 4: the recurrence as the reference writes it, one wavefront, rows in registers; removed, see CHANGELOG.md)
+ * spent ~35 VALU ops per cell, a third of them on things that are not the recurrence:
  * the gap-extension adds (e+E, f+E), a per-column multiple of E inside the lane's F aggregate, three per-cell selects that
  * put -10000 into the cells right of the band end, register moves that re-frame the previous row when the band start moves,
  * and a trace-byte computation the compiler sinks into the conditional store blocks (which keeps m, e, f, t of all C cells alive:
@@ -19,8 +20,16 @@
  *   - the row maximum: lanes entirely beyond the band end are masked after their local reduction; the one lane the band end cuts
  *     through checks whether its local arg-max fell on a cell beyond it and only then (rare: that cell is W columns off the running
  *     maximum) the wave repeats the reduction with per-cell masks.
- * The trace layout is that of wtz_extend_shift_reg and wtz_shift_traceback is shared; the byte holds the four decisions only - the "bases equal" bit (two ops per
- * cell to insert) is gone: the walk counts diagonal steps and gap runs, and matches / mismatches follow from the score (see wtz_shift_traceback<C, NL, false>).
+ * Trace layout (this file owns it; wtz_sw_frame16.h re-stages its nibbles into it, wtz_shift_traceback in wtz_sw_wave.h walks it): rows are carved from the
+ * transient pool 64 at a time (chunk table tr.chunk, one pointer per 64 rows); a row is zrow = ceil(C/4) * 256 bytes in the lane-transposed order
+ * (row, k/4, lane, k%4), so that each of the ceil(C/4) stores of a row writes 256 contiguous bytes; byte k of lane l belongs to band-relative column l*C + k
+ * and holds the four decisions only (bit 3 m<e, bit 2 max(m,e)<f, bit 1 E extended, bit 0 F extended); only lanes that own band cells store, what lies right
+ * of the band end is never read by the walk.  The band start of row i goes to zb[i].  The "bases equal" bit of the older form (two ops per cell to insert) is
+ * gone: the walk counts diagonal steps and gap runs, and matches / mismatches follow from the score (see wtz_shift_traceback<C, NL, false>).
+ * The once-per-64-rows block of the row loop (next trace chunk, next query words): every branch of it is wave-uniform BY CONSTRUCTION (readfirstlane) and it
+ * ends in an explicit vmcnt(0).  The wait-count pass works on the structurised CFG, and one vector load it believes may still be in flight when the row body
+ * starts makes every row wait for vmcnt(0) - i.e. for the previous row's trace stores, the latency this kernel hides.  For the same reason there is a vmcnt(0)
+ * in front of the loop: a load still pending at loop entry would otherwise be waited for inside every row.
  * Values are kept < 2^20 in magnitude (caller's envelope, which now includes (ql+tl)*|E| for the frame term) so that the packed
  * arg-max key  H*2048 + (2047 - band column)  fits 32 bits in every intermediate form.
  */
@@ -193,7 +202,7 @@ WTZ_D wtz_aln_t wtz_extend_shift_fr(int32_t qlen, const wtz_seq_packed &query, i
 	__builtin_amdgcn_s_waitcnt(0x0F70);
 	for(i = 0; i < ql; i++){
 		if((i & 63) == 0){
-			/* every branch of this block is wave-uniform by construction and the block ends in an explicit vmcnt(0): see wtz_extend_shift_reg */
+			/* every branch of this block is wave-uniform by construction and the block ends in an explicit vmcnt(0): see the head of this file */
 			const uint32_t ci = (uint32_t)i >> 6;
 			unsigned long long za = 0;
 			const int have = __builtin_amdgcn_readfirstlane(ci < tr.n_chunk ? 1 : 0);
@@ -332,7 +341,7 @@ WTZ_D wtz_aln_t wtz_extend_shift_fr(int32_t qlen, const wtz_seq_packed &query, i
 }
 
 /* one K-sw3 job on the calling wavefront in the frame form; false = the job is outside the envelope (or its counts did not follow from the score) and stays
- * open for the older forms (wtz_kernel_extjobs_reg / wtz_kernel_extjobs).  stb: TW 64-bit words of LDS of this wave. */
+ * open for the general kernel (wtz_kernel_extjobs).  stb: TW 64-bit words of LDS of this wave. */
 template<int TW, int CLO, int CHI>
 WTZ_D bool wtz_extjob_run_fr(wtz_extjob_t *job, const wtz_params_t *Pm, wtz_pool_t *pool, wtz_pool_t *tpool, uint64_t *stb){
 	if(!job->valid || job->done) return true;

@@ -310,7 +310,7 @@ WTZ_D wtz_aln_t wtz_extend_shift_pk(int32_t qlen, const wtz_seq_packed &query, i
 	__builtin_amdgcn_s_waitcnt(0x0F70);
 	for(i = 0; i < ql; i++){
 		if((i & 63) == 0){
-			/* every branch of this block is wave-uniform by construction and the block ends in an explicit vmcnt(0): see wtz_extend_shift_reg */
+			/* every branch of this block is wave-uniform by construction and the block ends in an explicit vmcnt(0): see the head of wtz_sw_frame.h */
 			const uint32_t ci = (uint32_t)i >> 6;
 			unsigned long long za = 0;
 			const int have = __builtin_amdgcn_readfirstlane(ci < tr.n_chunk ? 1 : 0);

@@ -37,9 +37,6 @@ typedef struct {
 	wtz_aln_t x; uint32_t *cigar; uint32_t cigar_len; int32_t bad; unsigned long long cells;
 } wtz_extjob_t;
 
-#ifndef WTZ_OCC_EXTREG
-#define WTZ_OCC_EXTREG 1
-#endif
 #ifndef WTZ_WINALIGN_LDS_BYTES
 #define WTZ_WINALIGN_LDS_BYTES 12288     /* LDS slice of a window-alignment wave (measured best with 3 waves/SIMD) */
 #endif
@@ -499,7 +496,7 @@ WTZ_D void wtz_cigw_push(wtz_cigw_t &w, uint32_t op, uint32_t len){
 }
 WTZ_D void wtz_cigw_finish(wtz_cigw_t &w){ if(w.tail){ w.v->push(w.tail); w.tail = 0; } }
 
-/* ---- traceback of the K-sw3 register forms (one wavefront; NL = lanes of a trace row: 64, or 256 for the four-wave form).
+/* ---- traceback of the K-sw3 register forms (one wavefront; NL = lanes of a trace row: 64).
  * The trace lives in the pool in the lane-transposed layout (row, k/4, lane, k%4).  Lane 0 walks, but never against HBM latency:
  * for the 64 rows below the current cell the wave copies the dwords of the NLW lanes around the current band-relative column
  * into LDS - one row per step, lane x takes dword (x / C4, x % C4) of the row, so a step is a few contiguous pieces and the loads
@@ -620,247 +617,13 @@ WTZ_D bool wtz_shift_traceback(wtz_aln_t &x, uint8_t **zchunk, const int32_t *zb
 	return __builtin_amdgcn_readfirstlane((int)consistent) != 0;
 }
 
-/*
- * K-sw3 with the DP rows entirely in registers (the form the job kernel runs; wtz_extend_shift_wave_rt above is its
- * fallback and on-device cross-check).  Lane l owns the C band-relative columns l*C .. l*C+C-1.  The band start moves
- * by s = 0, 1 or 2 columns per row (kswx.h:186-199), so H(i-1,j-1) and E(i-1,j) of the new frame are the lane's own
- * registers at a compile-time offset (k+s-1, k+s) plus at most two values of the next lane / one of the previous lane,
- * fetched with wave_shl / wave_shr DPP moves: three fully unrolled row bodies, no LDS hand-over.  Cells are branch-free;
- * the row maximum and its FIRST arg-max come from one max-reduction over keys h*2048 + (2047 - band column) (callers
- * guarantee |h| < 2^20); the query row base is scalar (32-base words in VGPRs, v_readlane every 16 rows); LDS holds only
- * the 2-bit target.  Trace bytes, band starts and traceback are those of the rt form.
- */
+/* ---- building blocks of the K-sw3 forms that keep the DP rows entirely in registers (wtz_sw_frame.h, wtz_sw_frame16.h; wtz_extend_shift_wave_rt above is
+ * their fallback and on-device cross-check) ---- */
 template<int V> struct wtz_ic { static constexpr int value = V; };
 template<int I, int N, typename F> WTZ_D void wtz_static_for(F &&f){ if constexpr(I < N){ f(wtz_ic<I>{}); wtz_static_for<I + 1, N>(f); } }
 /* a*b + c with 24-bit a, b in ONE VALU op; the asm keeps the compiler from turning a 0/1 factor into compare+select or from
  * hoisting the (wave-uniform) product into a scalar register per cell */
 WTZ_D int32_t wtz_mad24(int32_t a, int32_t b, int32_t c){ int32_t r; asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-template<int K>
-WTZ_D int32_t wtz_mad24_imm(int32_t b, int32_t c){ int32_t r; asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "n"(K), "v"(b), "v"(c)); return r; }
-template<int CMAX, int S>
-WTZ_D void wtz_shift_row_inputs(int32_t (&hv)[CMAX], int32_t (&ev)[CMAX], int lane, int32_t bnd){
-	/* rewrite hv := H(i-1, j-1), ev := E(i-1, j) for the new frame j = j0_old + S + k, in place */
-	if(S == 0){
-		int32_t prv = wtz_dpp_wave_shr1(-10000, hv[CMAX - 1]);
-		prv = (lane == 0) ? bnd : prv;
-		#pragma unroll
-		for(int k = CMAX - 1; k > 0; k--) hv[k] = hv[k - 1];
-		hv[0] = prv;
-	} else if(S == 1){
-		const int32_t ne0 = wtz_dpp_wave_shl1(-10000, ev[0]);
-		#pragma unroll
-		for(int k = 0; k + 1 < CMAX; k++) ev[k] = ev[k + 1];
-		ev[CMAX - 1] = ne0;
-	} else {
-		const int32_t nh0 = wtz_dpp_wave_shl1(-10000, hv[0]);
-		const int32_t ne0 = wtz_dpp_wave_shl1(-10000, ev[0]), ne1 = wtz_dpp_wave_shl1(-10000, ev[1]);
-		#pragma unroll
-		for(int k = 0; k + 1 < CMAX; k++) hv[k] = hv[k + 1];
-		hv[CMAX - 1] = nh0;
-		#pragma unroll
-		for(int k = 0; k + 2 < CMAX; k++) ev[k] = ev[k + 2];
-		ev[CMAX - 2] = ne0; ev[CMAX - 1] = ne1;
-	}
-}
-
-template<int CMAX>
-WTZ_D wtz_aln_t wtz_extend_shift_reg(int32_t qlen, const wtz_seq_packed &query, int32_t tlen, const wtz_seq_packed &target, int32_t init_score,
-		int32_t ql, int32_t tl, int32_t W, int32_t M, int32_t X, int32_t I, int32_t D, int32_t E, int32_t T,
-		uint64_t *tb, wtz_trace_t &tr, wtz_pool_t *pool, wtz_cigar_t &cigars, unsigned long long *cells, bool *ok){
-	const int lane = (int)(threadIdx.x & 63);
-	wtz_aln_t x; memset(&x, 0, sizeof x);
-	*ok = true;
-	if(lane == 0) cigars.n = 0;
-	if(init_score < 0) init_score = 0;
-	constexpr int C = CMAX;                       /* the lane block is exactly CMAX wide: 64*CMAX >= n_col */
-	constexpr int C4 = (C + 3) / 4;
-	const uint32_t zrow = (uint32_t)C4 * 256u;
-	if(!wtz_trace_prepare(tr, pool, zrow, ql, true)){ *ok = false; return x; }
-	uint8_t **zchunk = tr.chunk; int32_t *zb = tr.zb;
-	uint8_t *z = NULL;
-	{
-		const int32_t nw = (tl + 31) / 32 + 1;
-		for(int32_t w = lane; w < nw; w += 64) tb[w] = wtz_pack32(target, w * 32, tl);
-	}
-	__threadfence_block();
-	int32_t hv[C], ev[C];
-	#pragma unroll
-	for(int k = 0; k < C; k++){ hv[k] = -10000; ev[k] = -10000; }
-	int32_t mx = init_score, mi = -1, mj = -1, gmax = 0, gi = -1, gj = -1;
-	int32_t jbp = 0, c = 0, i;
-	unsigned long long ncell = 0;
-	const int32_t CE = C * E, IE = I + E, DE = D + E;
-	uint32_t qw_lo = 0, qw_hi = 0, qcur = 0;
-	const int32_t colrel0 = lane * C;
-	int32_t jb_n = 0, je_n = tl; uint64_t tbits_n;
-	{
-		if(je_n > W + 1) je_n = W + 1;              /* row 0: c = 0 */
-		if(je_n > tl) je_n = tl;
-		const int32_t jj = colrel0 < tl ? colrel0 : (tl > 0 ? tl - 1 : 0);
-		const int32_t w = jj >> 5, sh = (jj & 31) * 2;
-		const uint64_t w0 = tb[w], w1 = tb[w + 1];
-		tbits_n = sh ? ((w0 >> sh) | (w1 << (64 - sh))) : w0;
-	}
-	__builtin_amdgcn_s_waitcnt(0x0F70);              /* vmcnt(0) before the loop: a load still pending at loop entry would otherwise be waited for inside every row */
-	for(i = 0; i < ql; i++){
-		if((i & 63) == 0){
-			/* Every branch of this block is wave-uniform BY CONSTRUCTION (readfirstlane) and the block ends in an explicit vmcnt(0): the
-			 * wait-count pass works on the structurised CFG, and one vector load it believes may still be in flight when the row body
-			 * starts makes every row wait for vmcnt(0) -- i.e. for the previous row's trace stores, the latency this kernel hides. */
-			const uint32_t ci = (uint32_t)i >> 6;
-			unsigned long long za = 0;
-			const int have = __builtin_amdgcn_readfirstlane(ci < tr.n_chunk ? 1 : 0);
-			if(have) za = (unsigned long long)(uintptr_t)wtz_as_global(zchunk)[ci];
-			else {
-				if(lane == 0){ uint8_t *p = (uint8_t*)wtz_pool_alloc(pool, (size_t)zrow * 64); wtz_as_global(zchunk)[ci] = p; za = (unsigned long long)(uintptr_t)p; }
-				za = __shfl(za, 0, 64);
-			}
-			const uint32_t zlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)za), zhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(za >> 32));
-			z = (uint8_t*)(uintptr_t)(((unsigned long long)zhi << 32) | zlo);
-			if((zlo | zhi) == 0){ *ok = false; break; }
-			if(!have) tr.n_chunk = ci + 1;
-			if((i & 2047) == 0){ const uint64_t qw = wtz_pack32(query, i + lane * 32, ql); qw_lo = (uint32_t)qw; qw_hi = (uint32_t)(qw >> 32); }
-			__builtin_amdgcn_s_waitcnt(0x0F70);          /* vmcnt(0), once per 64 rows */
-		}
-		/* band and target bases of THIS row were prepared at the end of the previous iteration (see below) */
-		const int32_t jb = jb_n, je = je_n;
-		if((i & 15) == 0){
-			const int32_t qs = __builtin_amdgcn_readfirstlane((i & 2047) >> 5);
-			qcur = (i & 16) ? (uint32_t)__builtin_amdgcn_readlane((int)qw_hi, qs) : (uint32_t)__builtin_amdgcn_readlane((int)qw_lo, qs);
-		}
-		const uint32_t qbase = (qcur >> ((i & 15) * 2)) & 3u;
-		const int32_t j0 = jb + colrel0;
-		const uint64_t tbits = tbits_n;
-		/* ---- previous row into the new frame ---- */
-		if(i == 0){
-			#pragma unroll
-			for(int k = 0; k < C; k++){ const int32_t j = j0 + k; hv[k] = (j == 0) ? init_score : init_score + D + E * j; }     /* rh[] initialisation, kswx.h:143-144; E stays -10000 */
-		} else {
-			const int32_t s = jb - jbp;
-			const int32_t bnd = (jb == 0) ? init_score + I + E * i : -10000;      /* H(i-1, jb-1): outside the previous band unless it is column -1 */
-			if(s == 0) wtz_shift_row_inputs<C, 0>(hv, ev, lane, bnd);
-			else if(s == 1) wtz_shift_row_inputs<C, 1>(hv, ev, lane, bnd);
-			else wtz_shift_row_inputs<C, 2>(hv, ev, lane, bnd);
-		}
-		/* The cells are instruction-issue bound (a lone wave retires one VALU op per 4 cycles), so every op per cell counts:
-		 *  - base equality comes from one 64-bit XOR per row (eqw: bit 2k set where query base == target base k), not a compare per cell;
-		 *  - the lane's F aggregate needs no validity mask: the cells right of the band end only feed lanes right of the band end;
-		 *  - the four decisions are pushed into the trace byte as the sign bit of a difference (v_sub + v_alignbit), no compare/select;
-		 *  - the arg-max key is taken from the masked H (the stored -10000 never wins) and the lane's column offset is added once.
-		 * Trace byte of this kernel (decoded when the traceback stages it): bit 4 m<e, bit 3 max(m,e)<f, bit 2 E extended, bit 1 F extended, bit 0 bases equal. */
-		const int32_t nv = je - j0;                        /* cell k of this lane is inside the band iff k < nv */
-		uint32_t eq_lo, eq_hi;
-		{
-			const uint32_t qrep = 0x55555555u * qbase;
-			const uint32_t x_lo = (uint32_t)tbits ^ qrep, x_hi = (uint32_t)(tbits >> 32) ^ qrep;
-			eq_lo = ~(x_lo | (x_lo >> 1)) & 0x55555555u; eq_hi = ~(x_hi | (x_hi >> 1)) & 0x55555555u;
-		}
-		const int32_t MX = M - X, nE = -E;
-		/* ---- m in place, the lane's F aggregate ---- */
-		int32_t agg = -0x3FFFFFFF;
-		wtz_static_for<0, C>([&](auto kc){
-			constexpr int k = decltype(kc)::value;
-			const int32_t b = (int32_t)(((k < 16 ? eq_lo : eq_hi) >> (2 * (k & 15))) & 1u);
-			const int32_t m = wtz_mad24(b, MX, hv[k]) + X;
-			hv[k] = m;
-			const int32_t cand = wtz_mad24_imm<k>(nE, m);          /* m - k*E: the common DE + (C-1)*E is added after the loop */
-			agg = cand > agg ? cand : agg;
-		});
-		agg += DE + (C - 1) * E;
-		int32_t f;
-		{
-			const int32_t g = agg - lane * CE;
-			const int32_t pm = wtz_wave_max_scan_excl(g, -0x3FFFFFFF);
-			const int32_t from_prev = (lane == 0) ? -0x3FFFFFFF : pm + (lane - 1) * CE;
-			const int32_t from_init = -10000 + lane * CE;
-			f = from_prev > from_init ? from_prev : from_init;
-		}
-		/* ---- H, E', F, trace byte ---- */
-		int32_t key = -0x40000000, kg = -0x40000000;
-		uint32_t zw[C4];
-		#pragma unroll
-		for(int q4 = 0; q4 < C4; q4++) zw[q4] = 0;
-		#pragma unroll
-		for(int k = 0; k < C; k++){
-			const bool valid = (k < nv);
-			const int32_t m = hv[k], e = ev[k];
-			const int32_t h0 = m > e ? m : e;
-			uint32_t d = (uint32_t)(m - e) >> 31;                                              /* m < e */
-			d = __builtin_amdgcn_alignbit(d, (uint32_t)(h0 - f), 31);                          /* max(m,e) < f */
-			const int32_t h = h0 > f ? h0 : f;
-			const int32_t te = m + IE, e2 = e + E;
-			d = __builtin_amdgcn_alignbit(d, (uint32_t)(te - e2), 31);                         /* e + E > m + I + E */
-			const int32_t en = e2 > te ? e2 : te;
-			const int32_t tf = m + DE, f2 = f + E;
-			d = __builtin_amdgcn_alignbit(d, (uint32_t)(tf - f2), 31);                         /* f + E > m + D + E */
-			f = f2 > tf ? f2 : tf;
-			d = (d << 1) | (((k < 16 ? eq_lo : eq_hi) >> (2 * (k & 15))) & 1u);
-			const int32_t hm = valid ? h : -10000;
-			hv[k] = hm; ev[k] = valid ? en : -10000;
-			/* arg-max key h*2048 + (2047 - column): inside a group of 16 cells the column term is an inline constant of v_lshl_add_u32 */
-			const int32_t kk = (int32_t)(((uint32_t)hm << 11) + (uint32_t)(-(k & 15)));
-			kg = kk > kg ? kk : kg;
-			if((k & 15) == 15 || k == C - 1){ const int32_t t = kg - (k & ~15); key = t > key ? t : key; kg = -0x40000000; }
-			zw[k >> 2] |= (valid ? d : 0u) << (8 * (k & 3));
-		}
-		key += 2047 - colrel0;
-		ncell += (unsigned long long)(je - jb);
-		key = wtz_wave_max_i32(key);
-		int32_t imax = 0, mj2 = -1;
-		if((key >> 11) > 0){ imax = key >> 11; mj2 = jb + (2047 - (key & 2047)); }       /* first j with the maximum, only if > 0 (kswx.h:172) */
-		if(lane == 0) wtz_as_global(zb)[i] = jb;
-		if(je == tlen){
-			const int32_t idx = je - 1 - jb, kl = idx % C;
-			int32_t hsel = hv[0];
-			#pragma unroll
-			for(int k = 1; k < C; k++) hsel = (kl == k) ? hv[k] : hsel;
-			const int32_t h1 = __builtin_amdgcn_readlane(hsel, __builtin_amdgcn_readfirstlane(idx / C));      /* H(i, je-1) */
-			if(gmax < h1){ gmax = h1; gi = i; gj = je - 1; }
-		}
-		if(i + 1 == qlen && gmax < imax){ gmax = imax; gi = i; gj = mj2; }
-		jbp = jb;
-		bool stop = false;
-		if(imax > mx){ mx = imax; mi = i; mj = mj2; }
-		else if(imax <= 0) stop = true;
-		if(!stop){
-			c++; if(c < mj2) c++; else if(c > mj2) c--;
-			/* next row's band and its target bases (LDS) BEFORE this row's trace goes out: the wait the compiler puts in front of
-			 * an LDS read then only covers the stores of the previous row, which have had a whole row to complete */
-			jb_n = 0; je_n = tl;
-			if(jb_n < c - W) jb_n = c - W;
-			if(je_n > c + W + 1) je_n = c + W + 1;
-			if(je_n > tl) je_n = tl;
-			const int32_t j0n = jb_n + colrel0;
-			const int32_t jj = j0n < tl ? j0n : (tl > 0 ? tl - 1 : 0);
-			const int32_t w = jj >> 5, sh = (jj & 31) * 2;
-			const uint64_t w0 = tb[w], w1 = tb[w + 1];
-			tbits_n = sh ? ((w0 >> sh) | (w1 << (64 - sh))) : w0;
-		}
-		{
-			WTZ_GLOBAL_AS uint32_t *zr = wtz_as_global((uint32_t*)(z + (size_t)(i & 63) * zrow) + lane);
-#ifndef WTZ_EXP_NOTRACE
-			/* only the lanes that own band cells store: the bytes right of the band end are never read by the walk (E and H are -10000 there,
-			 * no path enters them), and in the first rows of an extension half of the lane blocks lie beyond it - the trace stores were a
-			 * quarter of this kernel's time (diagnostic builds without them: K-sw3 stage 927 -> 702 ms at configs[2]) */
-			#pragma unroll
-			for(int q4 = 0; q4 < C4; q4++) if(q4 * 4 < nv) zr[(size_t)q4 * 64] = zw[q4];
-#else
-			if(zw[0] == 0xFFFFFFFFu && zw[C4 - 1] == 0xFFFFFFFEu) zr[0] = 1;     /* diagnostic build: never true, keeps the trace computation alive */
-#endif
-		}
-		if(stop) break;
-	}
-	if(cells && lane == 0) *cells += ncell;
-	if(!*ok) return x;
-	if(gmax > 0 && gmax >= mx + T){ x.score = gmax; x.qe = gi; x.te = gj; }
-	else { x.score = mx; x.qe = mi; x.te = mj; }
-	__threadfence_block();     /* the trace was written by lanes of THIS wave: ordering inside the wave is enough (an agent-scope fence would write back the whole L2) */
-	const unsigned long long pt_tb3 = WTZ_PROF_T(); (void)pt_tb3;
-	WTZ_PROF_CNT(60, i < ql ? i + 1 : ql); WTZ_PROF_CNT(61, 1);
-	wtz_shift_traceback<C, 64>(x, zchunk, zb, zrow, tb, cigars);
-	WTZ_PROF_ADD(9, pt_tb3);
-	return wtz_bcast_aln(x);
-}
 
 /* ---- K-sw3 jobs: one wave (64 threads) per job; jobs that do not fit the LDS rings run the scalar body on lane 0 ---- */
 template<int P, int TW>
@@ -897,55 +660,6 @@ __global__ void __launch_bounds__(64) wtz_kernel_extjobs(wtz_extjob_t *jobs, con
 		job->x = x; job->cigar = cg.a; job->cigar_len = cg.n; job->bad = (mem.bad || cg.bad); job->cells = cells; job->done = 3;
 	}
 }
-
-/* K-sw3 jobs through the register DP: LDS carries only the 2-bit target.  Jobs outside its envelope (band wider than
- * 64*32 columns, target longer than the LDS words, scores beyond the packed-key range) are left for wtz_kernel_extjobs. */
-/* CLO < columns per lane <= CHI: the whole envelope is <TW, 0, 32>; the launch may be split by band class (run_extjobs) so that the narrow
- * bands run from a kernel with a smaller register budget and a smaller instruction footprint */
-template<int TW, int CLO = 0, int CHI = 32>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CHI <= 16 ? 2 : WTZ_OCC_EXTREG, 8))) wtz_kernel_extjobs_reg(wtz_extjob_t *jobs, const uint32_t *order, uint32_t n, const wtz_params_t *Pm, wtz_pool_t *pool, wtz_pool_t *tpool){
-	__shared__ uint64_t stb[TW];
-	const uint32_t b = blockIdx.x;
-	if(b >= n) return;
-	wtz_extjob_t *job = &jobs[order ? order[b] : b];
-	if(!job->valid) return;
-	const int lane = (int)(threadIdx.x & 63);
-	if(job->qlen <= 0 || job->tlen <= 0) return;
-	const unsigned long long pt_job = WTZ_PROF_T(); (void)pt_job;
-	const int32_t init_score = job->init_score < 0 ? 0 : job->init_score;
-	int32_t W = job->W, ql, tl, n_col;
-	wtz_ext_geometry(job->qlen, job->tlen, init_score, W, Pm->M, Pm->O, Pm->O, Pm->E, Pm->T, ql, tl, n_col);
-	const int32_t Cw = (n_col + 63) / 64;
-	if(Cw > 32 || (tl + 63) / 32 + 1 > TW || (ql + 63) / 64 > WTZ_TRACE_MAXCHUNK) return;
-	if((long long)init_score + (long long)Pm->M * (ql < tl ? ql : tl) >= (1 << 20)) return;
-	if(Cw <= CLO || (CHI < 32 && Cw > CHI)) return;        /* another launch's band class */
-	WTZ_PROF_BEGIN();
-	wtz_trace_t tr; tr.chunk = NULL; tr.zb = NULL; tr.n_chunk = 0; tr.zrow = 0; tr.cap_rows = 0;
-	wtz_cigar_t cg; cg.a = NULL; cg.n = cg.cap = 0; cg.pool = pool; cg.bad = 0;
-	if(lane == 0) cg.init(pool, (uint32_t)ql / 2u + 16u);
-	unsigned long long cells = 0; bool ok = true;
-	wtz_aln_t x;
-#define WTZ_EXTREG_CASE(CM) x = wtz_extend_shift_reg<CM>(job->qlen, job->q, job->tlen, job->t, job->init_score, ql, tl, W, Pm->M, Pm->X, Pm->O, Pm->O, Pm->E, Pm->T, stb, tr, tpool, cg, &cells, &ok)
-	if(Cw <= 4){ if(CLO < 4 && CHI >= 4) WTZ_EXTREG_CASE(4); }
-	else if(Cw <= 8){ if(CLO < 8 && CHI >= 8) WTZ_EXTREG_CASE(8); }
-	else if(Cw <= 12){ if(CLO < 12 && CHI >= 12) WTZ_EXTREG_CASE(12); }
-	else if(Cw <= 16){ if(CLO < 16 && CHI >= 16) WTZ_EXTREG_CASE(16); }
-	else if(Cw <= 20){ if(CLO < 20 && CHI >= 20) WTZ_EXTREG_CASE(20); }
-	else if(Cw <= 24){ if(CLO < 24 && CHI >= 24) WTZ_EXTREG_CASE(24); }
-	else if(Cw <= 28){ if(CLO < 28 && CHI >= 28) WTZ_EXTREG_CASE(28); }
-	else { if(CHI >= 32) WTZ_EXTREG_CASE(32); }
-#undef WTZ_EXTREG_CASE
-	if(lane == 0){ job->x = x; job->cigar = cg.a; job->cigar_len = cg.n; job->bad = (!ok || cg.bad); job->cells = cells; job->done = 1; }
-	WTZ_PROF_ADD(8, pt_job); WTZ_PROF_MAX(15, pt_job); WTZ_PROF_CNT(10, 1);
-	WTZ_PROF_END();
-}
-
-/* four int32 as one 128-bit LDS access, and the workgroup barrier of the multi-wave K-sw3 form (wtz_sw_frame_mw.h): the row's trace stores are NOT waited for */
-struct alignas(16) wtz_i4 { int32_t v[4]; };
-
-WTZ_D void wtz_mw_barrier(){ asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-/* (the round-4 four-wave kernel wtz_extend_shift_mw / wtz_kernel_extjobs_mw lived here: retired in round 6 - its frame-form successor is wtz_sw_frame_mw.h, DP form 6) */
 
 /*
  * K-sw1 for the small problems between two anchors of a window (80 % have a band of <= 64 columns, 96 % <= 128 rows):

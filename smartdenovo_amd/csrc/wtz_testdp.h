@@ -169,13 +169,11 @@ extern "C" int wtz_test_dp(wtz_ctx_t *c, int32_t kind, int32_t form, const wtz_d
 		wtz_extjob_t *d_jobs = NULL; CHK(dev_alloc((void**)&d_jobs, (size_t)n * sizeof(wtz_extjob_t))); CHK(dev_h2d(d_jobs, jobs.data(), (size_t)n * sizeof(wtz_extjob_t)));
 		wtz_timer tform; tform.start();      /* the forced forms report their launch time through counters.ms_ext too (tools/ubench/ksw3_bench.py) */
 		if(form == 0){ CHK(run_extjobs(c, V, d_jobs, n)); }
-		else if(form == 1){ hipLaunchKernelGGL((wtz_kernel_extjobs_reg<1032>), dim3(n), dim3(64), 0, g_stream, d_jobs, (const uint32_t*)NULL, n, V.P, V.pool, V.pool + 1); HIPCHK(hipGetLastError()); }
 		else if(form == 3){ hipLaunchKernelGGL((wtz_kernel_extjobs<2048, 1032>), dim3(n), dim3(64), 0, g_stream, d_jobs, (const uint32_t*)NULL, n, V.P, V.pool, V.pool + 1); HIPCHK(hipGetLastError()); }
 		else if(form == 4){ CHK(wtz_launch_wave<K_extjob_scalar>(0, n, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_extjob_scalar((uint32_t)t, V, d_jobs); })); }
 		else if(form == 5){ hipLaunchKernelGGL((wtz_kernel_extjobs_fr<1032>), dim3(n), dim3(64), 0, g_stream, d_jobs, (const uint32_t*)NULL, n, V.P, V.pool, V.pool + 1); HIPCHK(hipGetLastError()); }
-		else if(form == 6){ hipLaunchKernelGGL((wtz_kernel_extjobs_frmw<1032>), dim3(n), dim3(256), 0, g_stream, d_jobs, (const uint32_t*)NULL, n, V.P, V.pool, V.pool + 1); HIPCHK(hipGetLastError()); }      /* frame form on four wavefronts (round 6) */
 		else if(form == 7){ hipLaunchKernelGGL((wtz_kernel_extjobs_pk<1032>), dim3(n), dim3(64), 0, g_stream, d_jobs, (const uint32_t*)NULL, n, V.P, V.pool, V.pool + 1); HIPCHK(hipGetLastError()); }      /* frame form, two 16-bit cells per register (round 6) */
-		else return wtz_fail(WTZ_E_ARG, "WTZ_DP_SHIFT: unknown form %d", form);
+		else return wtz_fail(WTZ_E_ARG, "WTZ_DP_SHIFT: unknown form %d", form);      /* 1, 2 and 6 were kernels that have been removed: their numbers are not reused */
 		CHK(dev_sync());
 		if(form != 0){ c->cnt.ms_ext += tform.stop(); c->cnt.n_extjobs += n; }
 		CHK(tpool_check(c, "wtz_test_dp"));
@@ -184,7 +182,7 @@ extern "C" int wtz_test_dp(wtz_ctx_t *c, int32_t kind, int32_t form, const wtz_d
 			wtz_dpres_dev_t r; memset(&r, 0, sizeof r);
 			const int done = form == 4 ? 4 : (int)jobs[i].done;
 			const bool empty = jobs[i].qlen <= 0 || jobs[i].tlen <= 0;
-			/* the two register kernels leave empty problems (and what is outside their envelope) to the general kernel */
+			/* the register kernels leave empty problems (and what is outside their envelope) to the general kernel */
 			if(done || (form == 0) || (form == 3 && empty)){ r.x = jobs[i].x; r.cigar = jobs[i].cigar; r.cigar_len = jobs[i].cigar_len; r.form = done ? done : 3; r.bad = jobs[i].bad; r.cells = jobs[i].cells; }
 			hr[i] = r;
 		}

@@ -57,19 +57,17 @@ def check(vec, idx, out, cigs, kind, form, must):
     return answered
 
 
-# K-sw3: which forms must answer which class.  1 = one-wave register kernel (band <= 64 x 32 columns, target <= 1032 LDS words, key range),
-# (2 = the round-4 four-wave kernel: retired in round 6), 3 = LDS-ring kernel incl. its scalar fallback (everything), 4 = scalar body (everything),
-# 5 = one-wave kernel in the anti-diagonal frame (round 5, the product's one-wave form: same envelope as 1),
-# 6 = the frame form on four wavefronts (round 6; band <= 256 x 8), 7 = the frame form with two 16-bit cells per register (round 6: the product's first choice; same band envelope, values inside a 16-bit window)
+# K-sw3: which forms must answer which class.  3 = LDS-ring kernel incl. its scalar fallback (everything), 4 = scalar body (everything),
+# 5 = one-wave kernel in the anti-diagonal frame (round 5, the product's 32-bit one-wave form: band <= 64 x 32 columns, target <= 1032 LDS words, key range),
+# 7 = the frame form with two 16-bit cells per register (round 6: the product's first choice; same band envelope, values inside a 16-bit window).
+# 1 (round-4 one-wave register kernel), 2 (round-4 four-wave kernel) and 6 (frame form on four wavefronts) have been removed; their numbers are not reused.
 SHIFT_MUST = {
-    1: {"s_c1", "s_c4", "s_c8", "s_c12", "s_c16", "s_c20", "s_c24", "s_c28", "s_c32", "s_short", "s_rows", "s_stop", "s_end", "s_homo", "s_neginit"},
     5: {"s_c1", "s_c4", "s_c8", "s_c12", "s_c16", "s_c20", "s_c24", "s_c28", "s_c32", "s_short", "s_rows", "s_stop", "s_end", "s_homo", "s_neginit"},
-    6: {"s_c1", "s_c4", "s_c8", "s_c12", "s_c16", "s_c20", "s_c24", "s_c28", "s_c32", "s_short", "s_rows", "s_stop", "s_end", "s_homo", "s_neginit"},
     7: {"s_c1", "s_c4", "s_c8", "s_c12", "s_c16", "s_c20", "s_c24", "s_c28", "s_c32", "s_short", "s_rows", "s_stop", "s_end", "s_homo", "s_neginit"},
 }
 
 
-@pytest.mark.parametrize("form", [0, 1, 3, 4, 5, 6, 7])
+@pytest.mark.parametrize("form", [0, 3, 4, 5, 7])
 def test_shift_extension_forms(form, vec):
     idx = [int(i) for i in np.nonzero(vec.kind == 0)[0]]
     ctx = make_ctx(vec)
@@ -81,11 +79,27 @@ def test_shift_extension_forms(form, vec):
     ans = check(vec, idx, out, cigs, 0, form, must)
     if form == 0:       # the product's dispatch: the register kernels take what they can, the general kernel the rest
         used = {str(vec.cls[i]): int(out["form_used"][k]) for k, i in enumerate(idx)}
-        assert used["s_wide"] == 3 and used["s_keyovf"] in (3, 7) and used["s_longt"] == 3 and used["s_c4"] in (1, 5, 6, 7)
-    if form in (1, 5, 6, 7):  # outside the register kernels' envelope
+        assert used["s_wide"] == 3 and used["s_keyovf"] in (3, 7) and used["s_longt"] == 3 and used["s_c4"] in (5, 7)
+    if form in (5, 7):  # outside the register kernels' envelope
         # (the packed form keeps values relative to a per-job bias: an init_score near 2^20 is inside its window, and its answer is checked like any other)
         for cls in ("s_wide", "s_longt", "s_empty") + (() if form == 7 else ("s_keyovf",)):
             assert ans[cls][0] == 0, "form %d should decline %s" % (form, cls)
+
+
+def test_retired_shift_forms_are_argument_errors(vec):
+    """Forms 1, 2 and 6 named kernels that no longer exist: the ABI's argument error, and the context goes on working."""
+    idx = [int(i) for i in np.nonzero(vec.kind == 0)[0]]
+    ctx = make_ctx(vec)
+    try:
+        for form in (1, 2, 6):
+            with pytest.raises(RuntimeError, match=r"libwtzmo_hip error -1: .*unknown form %d" % form):
+                ctx.test_dp(hipabi.DP_SHIFT, form, problems(vec, idx))
+        out, cigs = ctx.test_dp(hipabi.DP_SHIFT, 5, problems(vec, idx))
+    finally:
+        ctx.close()
+    ans = check(vec, idx, out, cigs, 0, 5, lambda c: c in SHIFT_MUST[5])
+    for cls in ("s_wide", "s_longt", "s_empty", "s_keyovf"):
+        assert ans[cls][0] == 0, "form 5 should decline %s" % cls
 
 
 def _fixed_must(form, w):

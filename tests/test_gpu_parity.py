@@ -159,15 +159,11 @@ FORMS = [
     {"WTZ_WINALIGN_LANE": "0"},                       # K-sw1: every window on the chained wave kernel (round-2 form)
     {"WTZ_WINALIGN_LANE": "2"},                       # both K-sw1 paths, every window compared on the device (fails loudly on a difference)
     {"WTZ_GAP_LANE": "0"},                            # K-sw2: every gap on a wavefront
-    {"WTZ_CAND_WG": "0"},                             # seed lookup: wave per query, whole-query sort
-    {"WTZ_CAND_STREAM": "1", "WTZ_CAND_WG": "0"},     # seed lookup: sort-free accumulation
     {"WTZ_RANGE_OVERLAP": "0"},                       # host: strict plan -> compute -> commit order
     {"WTZ_BATCH_OVERLAP": "0"},                       # host: one batch at a time (ranges still pipelined)
     {"WTZ_BATCH_OVERLAP_GAIN": "1e9"},              # host: every batch formed in front of the commit before it, whatever the mask rate
-    {"WTZ_EXT_MW_ROWS": "600"},                       # K-sw3: the items whose extensions can run >= 600 rows on FOUR wavefronts each (frame form, wtz_sw_frame_mw.h) beside the fused launch
     {"WTZ_XCD_GROUP": "0"},                           # K_pair: identity block -> pair mapping
     {"WTZ_GAP_SIDESTREAM": "1"},                      # gaps on a side stream beside the left extensions
-    {"WTZ_WINALIGN4": "1"},                           # four windows per wavefront
     {"WTZ_SW_CHECK": "1"},                            # scalar body beside every wave DP
     {"WTZ_EXT_PK": "0"},                              # K-sw3: the 32-bit frame form alone (round 5-6), without the packed 16-bit form in front
     {"WTZ_EXT_FUSED": "0"},                           # K-sw3: the two end extensions in two launches with K_stitch_mid between them (rounds 1-4) instead of on one wavefront

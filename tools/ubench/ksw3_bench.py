@@ -2,11 +2,11 @@
 """K-sw3 in isolation: a seeded sample of the extension jobs of one configs[2] zmo step (geometry dumped by `WTZ_PROFILE_PAIR=1 WTZ_EXT_DUMP=... bench.py`,
 40 000 of 984 153 jobs: tools/ubench/ksw3_jobs_yeast100.npz) on synthetic homologous sequences (two 15 %-error copies of one random segment per job,
 aligned from their common start - what an end extension sees), run through the device forms of kswx_extend_align_shift_core via the test-only ABI entry
-wtz_test_dp:  1 = round-4 one-wave register kernel, 2 = four-wave kernel, 5 = one-wave kernel in the anti-diagonal frame (round 5), 6 = the frame form on four
-wavefronts (round 6), 0 = the product's dispatch.
-Every form's results are compared with form 1's (itself pinned to the reference's vectors by tests/test_gpu_dp_forms.py) - all fields and every CIGAR word.
+wtz_test_dp:  5 = one-wave kernel in the anti-diagonal frame (round 5), 7 = the same with two 16-bit cells per register (round 6), 3 = the general LDS-ring
+kernel, 0 = the product's dispatch.
+Every form's results are compared with those of the first form listed, by default form 5 (itself pinned to the reference's vectors by tests/test_gpu_dp_forms.py) - all fields and every CIGAR word.
 
-  python tools/ubench/ksw3_bench.py [--forms 1,5,0] [--jobs 40000] [--reps 3]
+  python tools/ubench/ksw3_bench.py [--forms 5,7,0] [--jobs 40000] [--reps 3]
 prints one JSON line per form: ms per pass (HIP events around the launches), G cells/s (cells as the reference loops execute them), fraction of the int32 roof.
 """
 import argparse, json, os, sys, time
@@ -24,7 +24,7 @@ def geometry(qlen, tlen, W=800):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--forms", default="1,5,0"); ap.add_argument("--jobs", type=int, default=40000); ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--forms", default="5,7,0"); ap.add_argument("--jobs", type=int, default=40000); ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--seed", type=int, default=7); ap.add_argument("--pool-gb", type=int, default=128); ap.add_argument("--chunk", type=int, default=40000)
     ap.add_argument("--no-compare", action="store_true", help="diagnostic library builds (no trace, no traceback ...) give wrong results by design")
     a = ap.parse_args()
