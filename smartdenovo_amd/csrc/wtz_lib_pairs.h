@@ -1,0 +1,215 @@
+/*
+ * wtz_lib_pairs.h — the per-batch pair stages in front of the alignment: wtz_batch_begin, wtz_pairs_seed (K_pair and the launches that finish what it
+ * leaves) and wtz_pairs_windows.  Included by wtz_lib.cpp.
+ */
+#ifndef WTZ_PAIR_DM_LDS_TIER2
+#define WTZ_PAIR_DM_LDS_TIER2 49152u
+#endif
+/* the last two launches keep only the band work arrays in LDS (the per-match image of a strand goes to the pool when it does not fit):
+ * what a heavy pair needs is resident waves, not LDS - a 159 KB slice meant ONE wave per CU, and the repeat-rich 40 Mbp set spent 14 of
+ * its 15 s there (159 KB: 13.8 s, 76: 7.1, 50: 5.0, 36: 4.1).  Tier 3 = eight waves per CU with room for ~2 000 linear groups per
+ * strand, tier 4 = four waves per CU with 8 191. */
+#ifndef WTZ_PAIR_DM_LDS_TIER3
+#define WTZ_PAIR_DM_LDS_TIER3 20480u
+#endif
+#ifndef WTZ_PAIR_DM_LDS_TIER4
+#define WTZ_PAIR_DM_LDS_TIER4 36864u
+#endif
+/* ------------------------------------------------------------------------------------------------ */
+/* per-batch pair stages                                                                             */
+/* ------------------------------------------------------------------------------------------------ */
+extern "C" int wtz_batch_begin(wtz_ctx_t *c){
+	if(!c) return wtz_fail(WTZ_E_ARG, "null context");
+	CTX_ENTER(c);
+	free_batch(c);
+	return pool_reset(c);
+}
+
+#if defined(WTZ_DEBUG_CRUMBS) && !defined(WTZ_EMUL)
+#include <signal.h>
+#include <unistd.h>
+static unsigned int *g_crumbs = NULL; static uint32_t g_crumbs_n = 0; static const uint32_t *g_crumbs_q = NULL, *g_crumbs_c = NULL;
+static void wtz_crumbs_dump(int sig){
+	unsigned hist[256]; memset(hist, 0, sizeof hist); unsigned shown = 0;
+	for(uint32_t i = 0; i < g_crumbs_n; i++) hist[g_crumbs[i] & 0xFF]++;
+	fprintf(stderr, "[crumbs] signal %d, %u pairs; tasks per last point:", sig, g_crumbs_n);
+	for(int k = 0; k < 256; k++) if(hist[k]) fprintf(stderr, " %d:%u", k, hist[k]);
+	fprintf(stderr, "\n");
+	for(uint32_t i = 0; i < g_crumbs_n && shown < 16; i++) if((g_crumbs[i] & 0xFF) != 0xFF && (g_crumbs[i] & 0xFF) != 0){ fprintf(stderr, "[crumbs]   pair %u (q %u, c %u): point %u, hits %u\n", i, g_crumbs_q[i], g_crumbs_c[i], g_crumbs[i] & 0xFF, g_crumbs[i] >> 8); shown++; }
+	fflush(stderr); _exit(86);
+}
+#endif
+
+extern "C" int wtz_pairs_seed(wtz_ctx_t *c, const uint32_t *qid, const uint32_t *cid, uint32_t n, wtz_pair_summary_t *out){
+	if(!c || !c->zs[0].have || (n && (!qid || !cid || !out))) return wtz_fail(WTZ_E_ARG, "z-index not built / null argument");
+	CTX_ENTER(c);
+	free_batch(c);
+	CHK(pool_reset(c));
+	if(n == 0){ c->n_pairs = 0; c->h_pairres.clear(); c->have_pairs = true; return WTZ_OK; }
+	for(uint32_t i = 0; i < n; i++) if(qid[i] >= c->n_reads || cid[i] >= c->n_reads) return wtz_fail(WTZ_E_ARG, "pair %u: read id out of range", i);
+	CHK(reserve_pairs(c, n));
+	CHK(dev_h2d(c->d_qid, qid, (size_t)n * 4)); CHK(dev_h2d(c->d_cid, cid, (size_t)n * 4));
+	const wtz_env_t V = ctx_env(c); const uint32_t *dq = c->d_qid, *dc = c->d_cid; wtz_pairres_t *dr = c->d_pairres;
+	wtz_timer tm; tm.start();
+	wtz_timer t1; t1.start();
+	STAGE(c, "K_pair");
+#if defined(WTZ_DEBUG_CRUMBS) && !defined(WTZ_EMUL)
+	unsigned int *h_crumbs = NULL;
+	if(getenv("WTZ_DEBUG_CRUMBS")){
+		HIPCHK(hipHostMalloc((void**)&h_crumbs, (size_t)n * 4, hipHostMallocCoherent | hipHostMallocMapped)); memset(h_crumbs, 0, (size_t)n * 4);
+		unsigned int *dptr = NULL; HIPCHK(hipHostGetDevicePointer((void**)&dptr, h_crumbs, 0));
+		HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(wtz_crumbs), &dptr, sizeof dptr));
+		g_crumbs = h_crumbs; g_crumbs_n = n; g_crumbs_q = qid; g_crumbs_c = cid;
+		signal(SIGABRT, wtz_crumbs_dump); signal(SIGPIPE, wtz_crumbs_dump); signal(SIGSEGV, wtz_crumbs_dump); signal(SIGBUS, wtz_crumbs_dump); signal(SIGTERM, wtz_crumbs_dump);
+	}
+#endif
+	/* XCD-aware task order: workgroups are dealt round-robin over the 8 XCDs, each with its own L2, and the pairs of a range are listed query by
+	 * query (about 30 candidates each), all of them searching the same query-side z-mer tables.  With the identity mapping an XCD's ~640 resident
+	 * waves hold every 8th pair of a 5 000-pair stretch, i.e. the tables of ~170 queries (20 MB against 4 MB of L2); giving every XCD runs of
+	 * `xg` CONSECUTIVE pairs makes that ~25 queries.  (WTZ_XCD_GROUP=0: identity.) */
+	const uint32_t xg = c->sw.xcd_group;
+	/* Heavy pairs first (round 4).  A pair's work grows faster than linearly with its matches (~ len(q) * len(c) / 78 732 chance matches of 10-mers alone), and
+	 * once the average dmo pair took a few ms the launch of a range ended with ONE wave still on a pair of 6 000 - 24 000 matches (100 - 230 M cycles of a
+	 * 120 - 170 ms launch: phase profile).  The n / 32 pairs with the largest len(q) * len(c) therefore head the task order (largest first); the others keep
+	 * the plan order - consecutive pairs share their query's tables - under the XCD mapping below.  WTZ_PAIR_HEAVY_FIRST=0 / 1 overrides the engine default
+	 * (dmo on; zmo off: its launches were measured full to the end). */
+	uint32_t nh = 0; const uint32_t *d_ord = NULL;
+#ifndef WTZ_EMUL
+	if(c->sw.heavy_first >= 0 ? c->sw.heavy_first != 0 : c->P.dot_matrix != 0){
+		nh = n / 32u;
+		if(nh >= 8u){
+			std::vector<uint64_t> key(n); std::vector<uint32_t> ord(n), hv(n);
+			for(uint32_t i = 0; i < n; i++){ key[i] = (uint64_t)c->h_rdlen[qid[i]] * c->h_rdlen[cid[i]]; hv[i] = i; }
+			std::nth_element(hv.begin(), hv.begin() + nh, hv.end(), [&](uint32_t a, uint32_t b){ return key[a] != key[b] ? key[a] > key[b] : a < b; });
+			std::sort(hv.begin(), hv.begin() + nh, [&](uint32_t a, uint32_t b){ return key[a] != key[b] ? key[a] > key[b] : a < b; });
+			std::vector<uint8_t> heavy(n, 0);
+			for(uint32_t k = 0; k < nh; k++){ ord[k] = hv[k]; heavy[hv[k]] = 1; }
+			uint32_t w = nh; for(uint32_t i = 0; i < n; i++) if(!heavy[i]) ord[w++] = i;
+			uint32_t *dd = NULL; CHK(dev_alloc((void**)&dd, (size_t)n * 4)); CHK(dev_h2d(dd, ord.data(), (size_t)n * 4)); d_ord = dd;
+		} else nh = 0;
+	}
+#endif
+	const uint64_t n64 = n - nh; const uint64_t nh64 = nh;
+#ifdef WTZ_EMUL
+	CHK(wtz_launch_coop<K_pair>(n, [=] WTZ_LAMBDA (uint64_t b){ (void)xg; (void)n64; (void)nh64; (void)d_ord; wtz_task_pair<-1>((uint32_t)b, V, dq, dc, dr); }, c->P.dot_matrix ? WTZ_PAIR_DM_LDS_BYTES : WTZ_PAIR_LDS_BYTES));
+#else
+	if(c->P.dot_matrix){
+		CHK(wtz_launch_coop<K_pair_dm>(n, [=] WTZ_LAMBDA (uint64_t b){
+			uint64_t t = b;
+			if(b >= nh64){ const uint64_t b2 = b - nh64; t = b2; if(xg){ const uint64_t per = 8ull * xg, full = n64 / per * per; if(b2 < full){ const uint64_t r = b2 % per; t = b2 - r + (r & 7u) * xg + (r >> 3); } } t += nh64; }
+			if(d_ord) t = d_ord[t];
+			wtz_task_pair<1>((uint32_t)t, V, dq, dc, dr); }, WTZ_PAIR_DM_LDS_BYTES));
+	} else {
+		CHK(wtz_launch_coop<K_pair>(n, [=] WTZ_LAMBDA (uint64_t b){
+			uint64_t t = b;
+			if(b >= nh64){ const uint64_t b2 = b - nh64; t = b2; if(xg){ const uint64_t per = 8ull * xg, full = n64 / per * per; if(b2 < full){ const uint64_t r = b2 % per; t = b2 - r + (r & 7u) * xg + (r >> 3); } } t += nh64; }
+			if(d_ord) t = d_ord[t];
+#ifdef WTZ_PAIR_TWO_LAUNCH
+			wtz_task_pair<0, false>((uint32_t)t, V, dq, dc, dr); }, WTZ_PAIR_LDS_BYTES));       /* experiment: pairs with ranges beyond the LDS slice are marked and finished by K_pair_zbig */
+#else
+			wtz_task_pair<0, true>((uint32_t)t, V, dq, dc, dr); }, WTZ_PAIR_LDS_BYTES));
+#endif
+	}
+#endif
+#if defined(WTZ_DEBUG_CRUMBS) && !defined(WTZ_EMUL)
+	if(h_crumbs){
+		const double t0 = wtz_wall(); const double limit = atof(getenv("WTZ_DEBUG_CRUMBS")) > 1 ? atof(getenv("WTZ_DEBUG_CRUMBS")) : 20.0;
+		while(hipStreamQuery(g_stream) == hipErrorNotReady && wtz_wall() - t0 < limit){ struct timespec ts = {0, 50000000}; nanosleep(&ts, NULL); }
+		if(hipStreamQuery(g_stream) == hipErrorNotReady){
+			unsigned hist[256]; memset(hist, 0, sizeof hist); unsigned shown = 0;
+			for(uint32_t i = 0; i < n; i++) hist[h_crumbs[i] & 0xFF]++;
+			fprintf(stderr, "[crumbs] K_pair still running after %.0f s, %u pairs; tasks per last point:", limit, n);
+			for(int k = 0; k < 256; k++) if(hist[k]) fprintf(stderr, " %d:%u", k, hist[k]);
+			fprintf(stderr, "\n");
+			for(uint32_t i = 0; i < n && shown < 12; i++) if((h_crumbs[i] & 0xFF) != 0xFF && (h_crumbs[i] & 0xFF) != 0){ fprintf(stderr, "[crumbs]   pair %u (q %u, c %u): point %u, hits %u\n", i, qid[i], cid[i], h_crumbs[i] & 0xFF, h_crumbs[i] >> 8); shown++; }
+			fflush(stderr); _exit(86);
+		}
+	}
+#endif
+	CHK(dev_sync());
+	{ const double ms1 = t1.stop(); if(c->sw.profile) fprintf(stderr, "[pair-profile] K_pair first launch: %u pairs, %.1f ms\n", n, ms1); }
+	c->n_pairs = n; c->h_pairres.resize(n); c->have_pairs = true;
+	CHK(dev_d2h(c->h_pairres.data(), c->d_pairres, (size_t)n * sizeof(wtz_pairres_t)));
+#ifndef WTZ_EMUL
+	if(!c->P.dot_matrix){
+		/* zmo pairs with a window range that does not fit the LDS slice (hundreds of matches of one strand inside one window: repeats) were left by the first launch:
+		 * the launch that carries the pool-workspace body of the scan finishes them (round 3 ran those scans on lane 0 and the heaviest pair bounded its launch) */
+		std::vector<uint32_t> list;
+		for(uint32_t i = 0; i < n; i++) if(c->h_pairres[i].gate && c->h_pairres[i].dm_dir == WTZ_PAIR_NEEDS_ZBIG && !c->h_pairres[i].bad) list.push_back(i);
+		if(!list.empty()){
+			uint32_t *d_list = NULL; CHK(dev_alloc((void**)&d_list, list.size() * 4)); CHK(dev_h2d(d_list, list.data(), list.size() * 4));
+			wtz_timer tt; tt.start();
+			STAGE(c, "K_pair_zbig");
+			CHK(wtz_launch_coop<K_pair_zbig>(list.size(), [=] WTZ_LAMBDA (uint64_t t){ wtz_task_pair<0, true>(d_list[t], V, dq, dc, dr); }, WTZ_PAIR_LDS_BYTES));
+			CHK(dev_sync());
+			const double ms_t = tt.stop();
+			CHK(dev_d2h(c->h_pairres.data(), c->d_pairres, (size_t)n * sizeof(wtz_pairres_t)));
+			if(c->sw.profile) fprintf(stderr, "[pair-profile] zmo pairs with ranges beyond the LDS slice: %zu of %u, %.1f ms\n", list.size(), n, ms_t);
+		}
+	}
+#endif
+	if(c->P.dot_matrix){
+		/* pairs whose strand images exceed the LDS slice of K_pair are finished by launches with larger slices: few pairs,
+		 * but they are the long ones that would otherwise bound the batch from a single lane */
+		uint32_t tiers[3] = { WTZ_PAIR_DM_LDS_TIER2, WTZ_PAIR_DM_LDS_TIER3, WTZ_PAIR_DM_LDS_TIER4 };
+		if(getenv("WTZ_DM_TIER3_KB")) tiers[1] = (uint32_t)atoi(getenv("WTZ_DM_TIER3_KB")) << 10;
+		if(getenv("WTZ_DM_TIER4_KB")) tiers[2] = (uint32_t)atoi(getenv("WTZ_DM_TIER4_KB")) << 10;
+		/* with the pool image allowed in the first launch only what overflowed its group table or band list is left: the last launch's */
+		for(int tier = c->sw.dm_first_big ? 2 : 0; tier < 3; tier++){
+			std::vector<uint32_t> list;
+			for(uint32_t i = 0; i < n; i++) if(c->h_pairres[i].gate && c->h_pairres[i].dm_dir == -2 && !c->h_pairres[i].bad) list.push_back(i);
+			if(list.empty()) break;
+			uint32_t *d_list = NULL; CHK(dev_alloc((void**)&d_list, list.size() * 4)); CHK(dev_h2d(d_list, list.data(), list.size() * 4));
+			const uint32_t lb = tiers[tier]; const bool last = (tier == 2), big = (tier >= 1);
+			wtz_timer tt; tt.start();
+			STAGE(c, "K_pair_big");
+			CHK(wtz_launch_coop<K_pair_big>(list.size(), [=] WTZ_LAMBDA (uint64_t t){ wtz_task_pair_dm_big((uint32_t)t, V, d_list, dq, dc, dr, lb, last, big); }, lb));
+			CHK(dev_sync());
+			const double ms_t = tt.stop();
+			CHK(dev_d2h(c->h_pairres.data(), c->d_pairres, (size_t)n * sizeof(wtz_pairres_t)));
+			if(c->sw.profile) fprintf(stderr, "[pair-profile] dmo tier %d (%u KB LDS): %zu pairs, %.1f ms\n", tier + 2, lb >> 10, list.size(), ms_t);
+		}
+	}
+	c->cnt.ms_pairs += tm.stop(); c->cnt.n_pairs += n;
+	for(uint32_t i = 0; i < n; i++) c->cnt.bytes_zmer_algo += (uint64_t)c->h_rdlen[cid[i]] / 4 + 16ull * c->h_pairres[i].n_hits;
+	CHK(pool_check(c, "wtz_pairs_seed"));
+	if(c->sw.profile){
+		uint64_t sum[4] = {0, 0, 0, 0}; uint32_t mx[4] = {0, 0, 0, 0}, arg = 0;
+		for(uint32_t i = 0; i < n; i++){ for(int k = 0; k < 4; k++){ sum[k] += c->h_pairres[i].tick[k]; if(c->h_pairres[i].tick[k] > mx[k]){ mx[k] = c->h_pairres[i].tick[k]; if(k == 3) arg = i; } } }
+		fprintf(stderr, "[pair-profile] n=%u kticks sum match/sort/win/total %llu/%llu/%llu/%llu max %u/%u/%u/%u; slowest pair: hits %u (its match/sort/win %u/%u/%u)\n", n,
+			(unsigned long long)sum[0], (unsigned long long)sum[1], (unsigned long long)sum[2], (unsigned long long)sum[3], mx[0], mx[1], mx[2], mx[3],
+			c->h_pairres[arg].n_hits, c->h_pairres[arg].tick[0], c->h_pairres[arg].tick[1], c->h_pairres[arg].tick[2]);
+	}
+	for(uint32_t i = 0; i < n; i++){
+		const wtz_pairres_t &r = c->h_pairres[i];
+		if(r.bad) return wtz_fail(WTZ_E_POOL, "wtz_pairs_seed: pair %u ran out of scratch", i);
+		wtz_pair_summary_t s; memset(&s, 0, sizeof s);
+		s.n_hits = r.n_hits; s.gate = r.gate; s.ovl[0] = r.ovl[0]; s.ovl[1] = r.ovl[1]; s.nwin[0] = r.nwin[0]; s.nwin[1] = r.nwin[1];
+		s.dm_score = r.dm_score; s.dm_qb = r.dm_qb; s.dm_qe = r.dm_qe; s.dm_tb = r.dm_tb; s.dm_te = r.dm_te; s.dm_dir = r.dm_dir;
+		out[i] = s;
+	}
+	return WTZ_OK;
+}
+
+extern "C" int wtz_pairs_windows(wtz_ctx_t *c, wtz_winbox_t *wins, uint64_t n_wins){
+	if(!c || !c->have_pairs) return wtz_fail(WTZ_E_STATE, "wtz_pairs_windows before wtz_pairs_seed");
+	CTX_ENTER(c);
+	uint64_t tot = 0; for(uint32_t i = 0; i < c->n_pairs; i++) tot += c->h_pairres[i].nwin[0] + c->h_pairres[i].nwin[1];
+	if(tot != n_wins) return wtz_fail(WTZ_E_ARG, "wtz_pairs_windows: expected room for %llu windows, got %llu", (unsigned long long)tot, (unsigned long long)n_wins);
+	if(tot == 0) return WTZ_OK;
+	if(!wins) return wtz_fail(WTZ_E_ARG, "null output");
+	std::vector<uint64_t> off((size_t)c->n_pairs * 2 + 1);
+	uint64_t o = 0; for(uint32_t i = 0; i < c->n_pairs; i++) for(int d = 0; d < 2; d++){ off[(size_t)i * 2 + d] = o; o += c->h_pairres[i].nwin[d]; }
+	off[(size_t)c->n_pairs * 2] = o;
+	uint64_t *d_off = NULL; wtz_winbox_t *d_w = NULL;
+	CHK(dev_alloc((void**)&d_off, off.size() * 8)); CHK(dev_h2d(d_off, off.data(), off.size() * 8));
+	CHK(dev_alloc((void**)&d_w, (size_t)tot * sizeof(wtz_winbox_t)));
+	const wtz_pairres_t *dr = c->d_pairres;
+	CHK(wtz_launch<K_pack_windows>((uint64_t)c->n_pairs * 2, [=] WTZ_LAMBDA (uint64_t t){
+		const wtz_pairres_t &r = dr[t >> 1]; const uint32_t d = (uint32_t)(t & 1);
+		for(uint32_t k = 0; k < r.nwin[d]; k++){ wtz_winbox_t b; b.beg[0] = r.win[d][k].beg[0]; b.beg[1] = r.win[d][k].beg[1]; b.end[0] = r.win[d][k].end[0]; b.end[1] = r.win[d][k].end[1]; d_w[d_off[t] + k] = b; }
+	}));
+	CHK(dev_sync());
+	CHK(dev_d2h(wins, d_w, (size_t)tot * sizeof(wtz_winbox_t)));
+	return WTZ_OK;
+}

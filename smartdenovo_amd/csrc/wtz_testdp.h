@@ -3,7 +3,7 @@
  * chosen device form of K-sw1 / K-sw2 / K-sw3 so that every form can be compared, function by function, with vectors dumped from the
  * reference's own kswx_extend_align_core (kswx.h:234), kswx_extend_align_shift_core (kswx.h:101) and ksw_global2 (ksw.c:503).
  * The forms are selected by the very functions the product kernels call (wtz_fixed_problem_wave, wtz_gap_problem_wave, run_extjobs and
- * the extension-job kernels); this file only wraps problems into their inputs and collects the results.  Included by wtz_lib.cpp.
+ * the extension-job kernels); this file only wraps problems into their inputs and collects the results.  Included by wtz_lib_batch.h.
  */
 #ifndef WTZ_TESTDP_H
 #define WTZ_TESTDP_H
@@ -149,16 +149,7 @@ extern "C" int wtz_test_dp(wtz_ctx_t *c, int32_t kind, int32_t form, const wtz_d
 	CHK(dev_d2h(h_off.data(), c->rdoff, (size_t)c->n_reads * 8));
 	for(uint32_t i = 0; i < n; i++){
 		const wtz_dp_problem_t &p = pr[i];
-		if(p.q_read >= c->n_reads || p.t_read >= c->n_reads) return wtz_fail(WTZ_E_ARG, "problem %u: read id out of range", i);
-		if((p.q_strand != 1 && p.q_strand != -1) || (p.t_strand != 1 && p.t_strand != -1)) return wtz_fail(WTZ_E_ARG, "problem %u: strand must be +1 or -1", i);
-		wtz_readview vq, vt;
-		vq.bits = c->bits; vq.off = h_off[p.q_read]; vq.len = c->h_rdlen[p.q_read]; vq.rev = p.q_rev ? 1u : 0u;
-		vt.bits = c->bits; vt.off = h_off[p.t_read]; vt.len = c->h_rdlen[p.t_read]; vt.rev = p.t_rev ? 1u : 0u;
-		const int64_t qlast = (int64_t)p.q_from + (int64_t)p.q_strand * (p.q_len > 0 ? p.q_len - 1 : 0), tlast = (int64_t)p.t_from + (int64_t)p.t_strand * (p.t_len > 0 ? p.t_len - 1 : 0);
-		if(p.q_len < 0 || p.t_len < 0 || (p.q_len > 0 && (p.q_from < 0 || p.q_from >= (int64_t)vq.len || qlast < 0 || qlast >= (int64_t)vq.len))
-				|| (p.t_len > 0 && (p.t_from < 0 || p.t_from >= (int64_t)vt.len || tlast < 0 || tlast >= (int64_t)vt.len)))
-			return wtz_fail(WTZ_E_ARG, "problem %u: region outside its read", i);
-		wtz_dpprob_dev_t d; d.q = vq.sub(p.q_from, p.q_strand); d.t = vt.sub(p.t_from, p.t_strand); d.qlen = p.q_len; d.tlen = p.t_len; d.init_score = p.init_score; d.W = p.W;
+		wtz_dpprob_dev_t d; CHK(dp_problem_views(c, h_off, p, i, true, 0, &d.q, &d.t)); d.qlen = p.q_len; d.tlen = p.t_len; d.init_score = p.init_score; d.W = p.W;
 		hp[i] = d;
 	}
 	const wtz_env_t V = ctx_env(c);
@@ -169,10 +160,10 @@ extern "C" int wtz_test_dp(wtz_ctx_t *c, int32_t kind, int32_t form, const wtz_d
 		wtz_extjob_t *d_jobs = NULL; CHK(dev_alloc((void**)&d_jobs, (size_t)n * sizeof(wtz_extjob_t))); CHK(dev_h2d(d_jobs, jobs.data(), (size_t)n * sizeof(wtz_extjob_t)));
 		wtz_timer tform; tform.start();      /* the forced forms report their launch time through counters.ms_ext too (tools/ubench/ksw3_bench.py) */
 		if(form == 0){ CHK(run_extjobs(c, V, d_jobs, n)); }
-		else if(form == 3){ hipLaunchKernelGGL((wtz_kernel_extjobs<2048, 1032>), dim3(n), dim3(64), 0, g_stream, d_jobs, (const uint32_t*)NULL, n, V.P, V.pool, V.pool + 1); HIPCHK(hipGetLastError()); }
-		else if(form == 4){ CHK(wtz_launch_wave<K_extjob_scalar>(0, n, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_extjob_scalar((uint32_t)t, V, d_jobs); })); }
-		else if(form == 5){ hipLaunchKernelGGL((wtz_kernel_extjobs_fr<1032>), dim3(n), dim3(64), 0, g_stream, d_jobs, (const uint32_t*)NULL, n, V.P, V.pool, V.pool + 1); HIPCHK(hipGetLastError()); }
-		else if(form == 7){ hipLaunchKernelGGL((wtz_kernel_extjobs_pk<1032>), dim3(n), dim3(64), 0, g_stream, d_jobs, (const uint32_t*)NULL, n, V.P, V.pool, V.pool + 1); HIPCHK(hipGetLastError()); }      /* frame form, two 16-bit cells per register (round 6) */
+		else if(form == 3){ WTZ_LAUNCH((wtz_kernel_extjobs<2048, 1032>), n, 64, 0, g_stream, d_jobs, (const uint32_t*)NULL, n, V.P, V.pool, V.pool + 1); }
+		else if(form == 4){ CHK(wtz_launch_wave<K_extjob_scalar>(n, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_extjob_scalar((uint32_t)t, V, d_jobs); })); }
+		else if(form == 5){ WTZ_LAUNCH((wtz_kernel_extjobs_fr<1032>), n, 64, 0, g_stream, d_jobs, (const uint32_t*)NULL, n, V.P, V.pool, V.pool + 1); }
+		else if(form == 7){ WTZ_LAUNCH((wtz_kernel_extjobs_pk<1032>), n, 64, 0, g_stream, d_jobs, (const uint32_t*)NULL, n, V.P, V.pool, V.pool + 1); }      /* frame form, two 16-bit cells per register (round 6) */
 		else return wtz_fail(WTZ_E_ARG, "WTZ_DP_SHIFT: unknown form %d", form);      /* 1, 2 and 6 were kernels that have been removed: their numbers are not reused */
 		CHK(dev_sync());
 		if(form != 0){ c->cnt.ms_ext += tform.stop(); c->cnt.n_extjobs += n; }
@@ -192,15 +183,15 @@ extern "C" int wtz_test_dp(wtz_ctx_t *c, int32_t kind, int32_t form, const wtz_d
 		CHK(dev_alloc((void**)&d_res, (size_t)n * sizeof(wtz_dpres_dev_t))); CHK(dev_set(d_res, 0, (size_t)n * sizeof(wtz_dpres_dev_t)));
 		const wtz_params_t *dP = c->dP; wtz_pool_t *pool = c->dpool;
 		if(kind == WTZ_DP_FIXED && form == 64){
-			CHK(wtz_launch_coop<K_test_lane>(0, n, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_test_lane((uint32_t)t, d_pr, dP, pool, d_res); }, 0));
+			CHK(wtz_launch_coop<K_test_lane>(n, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_test_lane((uint32_t)t, d_pr, dP, pool, d_res); }, 0));
 		} else if(kind == WTZ_DP_FIXED){
-			CHK(wtz_launch_coop<K_test_fixed>(0, n, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_test_fixed((uint32_t)t, d_pr, dP, pool, form, d_res); }, WTZ_WINALIGN_LDS_BYTES + WTZ_WINALIGN_QW_BYTES));
+			CHK(wtz_launch_coop<K_test_fixed>(n, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_test_fixed((uint32_t)t, d_pr, dP, pool, form, d_res); }, WTZ_WINALIGN_LDS_BYTES + WTZ_WINALIGN_QW_BYTES));
 		} else if(form == 64){
-			CHK(wtz_launch_coop<K_test_lane>(0, n, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_test_lane_global((uint32_t)t, d_pr, dP, pool, d_res); }, 0));
+			CHK(wtz_launch_coop<K_test_lane>(n, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_test_lane_global((uint32_t)t, d_pr, dP, pool, d_res); }, 0));
 		} else if(form == 33){
-			CHK(wtz_launch_coop<K_test_global_wide>(0, n, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_test_global((uint32_t)t, d_pr, dP, pool, form, (uint32_t)WTZ_GAP_WIDE_LDS_BYTES, d_res); }, WTZ_GAP_WIDE_LDS_BYTES));
+			CHK(wtz_launch_coop<K_test_global_wide>(n, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_test_global((uint32_t)t, d_pr, dP, pool, form, (uint32_t)WTZ_GAP_WIDE_LDS_BYTES, d_res); }, WTZ_GAP_WIDE_LDS_BYTES));
 		} else {
-			CHK(wtz_launch_coop<K_test_global>(0, n, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_test_global((uint32_t)t, d_pr, dP, pool, form, 0u, d_res); }, WTZ_GAP_LDS_BYTES));
+			CHK(wtz_launch_coop<K_test_global>(n, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_test_global((uint32_t)t, d_pr, dP, pool, form, 0u, d_res); }, WTZ_GAP_LDS_BYTES));
 		}
 		CHK(dev_sync());
 		CHK(dev_d2h(hr.data(), d_res, (size_t)n * sizeof(wtz_dpres_dev_t)));

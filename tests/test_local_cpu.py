@@ -123,3 +123,45 @@ def test_views_and_limits_on_the_emulated_device(emul_lib):
         assert lv.pool_info(ctx).main_used == 0
     finally:
         ctx.close()
+
+
+_BAD_PROBLEMS = [
+    ("read id out of range", lambda p, lens: p.__setitem__("q_read", len(lens)), "read id out of range"),
+    ("strand 0", lambda p, lens: p.__setitem__("t_strand", 0), r"strand must be \+1 or -1"),
+    ("region past the read end walking forwards", lambda p, lens: (p.__setitem__("q_from", 10), p.__setitem__("q_len", int(lens[0]) - 9)), "region outside its read"),
+    ("region past the read start walking backwards", lambda p, lens: (p.__setitem__("t_strand", -1), p.__setitem__("t_from", 20), p.__setitem__("t_len", 22)), "region outside its read"),
+    ("negative start", lambda p, lens: p.__setitem__("q_from", -1), "region outside its read"),
+]
+
+
+@pytest.mark.parametrize("entry", ["local", "extend"])
+@pytest.mark.parametrize("what,spoil,message", _BAD_PROBLEMS, ids=[b[0].replace(" ", "_") for b in _BAD_PROBLEMS])
+def test_bad_problems_are_the_same_argument_error_in_both_batch_entries(emul_lib, entry, what, spoil, message):
+    """wtz_local_batch and wtz_extend_batch turn a wtz_dp_problem_t into its two views by the same routine: the same bad problem (second of two, so the
+    message names problem 1) is WTZ_E_ARG (-1) with the same text from either, and the context goes on working"""
+    import ctypes as C
+    rng = np.random.default_rng(5)
+    seqs = [rng.integers(0, 4, 120).astype(np.uint8), rng.integers(0, 4, 90).astype(np.uint8)]
+    words, offs, lens = hipabi.pack_reads(seqs)
+    ctx = lv.make_context(words, offs, lens, 2, -5, lib_path=emul_lib)
+
+    def run(pr):
+        if entry == "local":
+            return ctx.local_batch(pr, *lv.GAPS[0])
+        pr = np.ascontiguousarray(pr, dtype=hipabi.DP_PROBLEM)
+        out = np.zeros(pr.size, dtype=hipabi.DP_RESULT)
+        cig = np.zeros(1 << 12, dtype=np.uint32)
+        ctx.lib.wtz_extend_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64]
+        ctx._chk(ctx.lib.wtz_extend_batch(ctx.h, pr.ctypes.data, pr.size, out.ctypes.data, cig.ctypes.data, cig.size))
+        return out
+
+    try:
+        pr = lv.whole_read_problems([0, 0], [1, 1], lens)
+        good = run(pr)
+        spoil(pr[1], lens)
+        with pytest.raises(RuntimeError, match=r"error -1: problem 1: " + message):
+            run(pr)
+        again = run(lv.whole_read_problems([0, 0], [1, 1], lens))
+        assert (again["score"] == good["score"]).all()
+    finally:
+        ctx.close()
