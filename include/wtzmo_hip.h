@@ -106,6 +106,8 @@ typedef struct {
 	uint64_t bytes_ingest_algo;                                                       /* 1 byte read + 2 bits written per base */
 	double   ms_local;                                                                /* K-local of wtz_local_batch (kernel time, copies excluded) */
 	uint64_t n_local, cells_local;                                                    /* its problems and the DP cells (rows x columns of both passes) it executed */
+	double   ms_kext;                                                                 /* K-kext of wtz_kext_batch and of the two extension stages of wtz_align_batch (kernel time, copies excluded) */
+	uint64_t n_kext, cells_kext;                                                      /* its problems and the DP cells (sum of end - beg over the rows executed) */
 } wtz_counters_t;
 
 const char *wtz_last_error(void);
@@ -260,6 +262,40 @@ int  wtz_extend_batch(wtz_ctx_t *ctx, const wtz_dp_problem_t *problems, uint32_t
  * executed.  The call takes 8 * t_len bytes of the main pool per problem whose query exceeds one strip (64 * form_used columns) and leaves the pool empty. */
 typedef struct { int32_t score, te, qe, tb, qb; uint32_t form_used; uint64_t cells; } wtz_local_result_t;
 int  wtz_local_batch(wtz_ctx_t *ctx, const wtz_dp_problem_t *problems, uint32_t n, int32_t o_del, int32_t e_del, int32_t o_ins, int32_t e_ins, wtz_local_result_t *out);
+
+/* ksw_extend2(qlen, query, tlen, target, 4, mat(M, X), o_del, e_del, o_ins, e_ins, w, end_bonus, zdrop, h0, &qle, &tle, &gtle, &gscore, &max_off) (ksw.c:381-478)
+ * for n independent problems on views of the uploaded reads: the extension with a clip bonus that kswx_extend_core (kswx.h:1386-1441) calls once per end of a
+ * local hit.  Rows run over the target, band columns over the query; the band is clamped as ksw.c:403-408 does, follows beg = max(beg, i - w),
+ * end = min(end, i + w + 1, qlen) and is trimmed after every row to the zeros around the row's LAST maximum (ksw.c:465-468); a row maximum of 0 (ksw.c:453) or,
+ * with zdrop > 0, the z-drop tests (ksw.c:458-462) end the DP.  32-bit arithmetic, no saturation.
+ * Problems are wtz_dp_problem_t views as for wtz_extend_batch: q_* is ksw_extend2's query, t_* its target (strand -1 from the far end = the reversed sequences of a
+ * left extension, kswx.h:1395), init_score = h0 (clamped at 0, ksw.c:386), W = w.  M and X are the context's params (1 <= M <= 127, -128 <= X <= 0), the gap
+ * costs are arguments: o_* >= 0, e_* >= 1 (the reference divides by them, ksw.c:403-406), open + extend <= 32767.
+ * out[i] = the return value (score) and the five outputs; rows = DP rows entered before the routine stopped, cells = sum of end - beg over them,
+ * form_used = band slots per lane of the kernel instantiation that ran it (1, 2, 4, 8, 16 or 32; chosen from min(w, t_len - 1) + min(w, q_len - 1) + 1 diagonals).
+ * LIMIT: 1 <= q_len, t_len <= WTZ_KEXT_MAXLEN (1 048 575), 0 <= W <= WTZ_KEXT_MAXW (1 023: 2 W + 1 diagonals on one wavefront), max(h0, 0) + q_len * M <= 2^30;
+ * anything else is WTZ_E_ARG for the whole call before anything is launched, and the context stays usable.  The call takes nothing from the pools and leaves the
+ * main pool empty. */
+#define WTZ_KEXT_MAXW 1023
+#define WTZ_KEXT_MAXLEN 0xFFFFF
+typedef struct { int32_t score, qle, tle, gtle, gscore, max_off; uint32_t form_used, rows; uint64_t cells; } wtz_kext_result_t;
+int  wtz_kext_batch(wtz_ctx_t *ctx, const wtz_dp_problem_t *problems, uint32_t n, int32_t o_del, int32_t e_del, int32_t o_ins, int32_t e_ins,
+                    int32_t end_bonus, int32_t zdrop, wtz_kext_result_t *out);
+
+/* kswx_align_no_stat(qlen, query, tlen, target, 4, mat(M, X), w, I, D, E, T) (kswx.h:1504-1511) for n independent problems as three device batches:
+ *   1  wtz_local_batch with (-D, -E, -I, -E) (kswx.h:1506); a problem whose qb, tb, qe or te is <= -1 is KSWR_NULL (kswx.h:36, 1507): found = 0, all else 0;
+ *      qe and te become exclusive (kswx.h:1508);
+ *   2  only when T < 0: every left extension (kswx.h:1390-1415), 3  every right extension (kswx.h:1417-1438), each from the score the step before left.
+ *      Per problem the longer remaining side is ksw_extend2's target and is cut to the other side + w; where the problem's target plays ksw_extend2's query the
+ *      opening costs change places (kswx.h:1407, 1431).  end_bonus = -T, zdrop = -1.  gscore <= 0 || gscore <= score + T keeps (qle, tle, score), otherwise the
+ *      extension runs to the end of the column side with (gtle, gscore).  An end already at 0 / at the sequence end is not extended (kswx.h:1391, 1418).
+ *      A stage is at most two K-kext launches groups (one per role), through the launch path of wtz_kext_batch.
+ * I, D, E, T as kswx_align receives them (costs as negative numbers, e.g. -3, -3, -1, -100): I, D <= 0, E <= -1; 0 <= w <= WTZ_KEXT_MAXW.  W and init_score of
+ * the problems are ignored.  out[i]: found, the extended rectangle [tb, te) x [qb, qe) and its score, and the local hit it grew from (local_te / local_qe
+ * exclusive too).  The limits of both underlying calls apply (1 <= q_len, t_len <= 65535) and are checked before anything runs: WTZ_E_ARG for the whole call.
+ * What kswx_align (kswx.h:1495-1502) does beyond this - one ksw_global2 over the rectangle with its statistics (kswx.h:1443-1482) - is not part of this call. */
+typedef struct { int32_t found, score, tb, te, qb, qe; int32_t local_score, local_tb, local_te, local_qb, local_qe; } wtz_align_result_t;
+int  wtz_align_batch(wtz_ctx_t *ctx, const wtz_dp_problem_t *problems, uint32_t n, int32_t w, int32_t I, int32_t D, int32_t E, int32_t T, wtz_align_result_t *out);
 
 /* Scratch accounting, so that the caller can size its batches to the pool instead of discovering the limit by WTZ_E_POOL:
  * the context's scratch is cut into a main pool (everything that lives for the batch: match lists, windows, CIGARs) and a transient

@@ -1,6 +1,6 @@
 /*
- * wtz_lib_batch.h — the DP routines as batch services for callers that hold their own problems: wtz_extend_batch (K-sw3), wtz_local_batch (K-local)
- * and, through wtz_testdp.h, the test-only wtz_test_dp.  Included by wtz_lib.cpp.
+ * wtz_lib_batch.h — the DP routines as batch services for callers that hold their own problems: wtz_extend_batch (K-sw3), wtz_local_batch (K-local),
+ * wtz_kext_batch (K-kext), wtz_align_batch (K-local + K-kext) and, through wtz_testdp.h, the test-only wtz_test_dp.  Included by wtz_lib.cpp.
  */
 /* the two sides of problem i as views of the uploaded reads (h_off: the reads' offsets, fetched by the caller), or WTZ_E_ARG.  allow_empty: a side of
  * length 0 is a problem like any other (its start is not looked at); max_len > 0: the longest side the caller's kernel takes */
@@ -143,6 +143,179 @@ extern "C" int wtz_local_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32_
 	CHK(pool_reset(c));
 	c->main_used_call = 0;
 	return WTZ_OK;
+}
+
+/* ------------------------------------------------------------------------------------------------ */
+/* ksw_extend2 as a batch service, and kswx_align_no_stat on top of it and of wtz_local_batch           */
+/* ------------------------------------------------------------------------------------------------ */
+/* the arguments every problem of a K-kext launch shares, or WTZ_E_ARG: scores as the reference's int8 matrix holds them, gap extensions >= 1 (ksw.c:403-406 divides by them) */
+static int kext_scores(const wtz_ctx *c, const char *who, int32_t o_del, int32_t e_del, int32_t o_ins, int32_t e_ins, int32_t zdrop, wtz_kextsc_t *S){
+	if(c->P.M < 1 || c->P.M > 127 || c->P.X > 0 || c->P.X < -128) return wtz_fail(WTZ_E_ARG, "%s: M must be in [1, 127] and X in [-128, 0]", who);
+	if(o_del < 0 || o_ins < 0 || e_del < 1 || e_ins < 1 || (int64_t)o_del + e_del > 32767 || (int64_t)o_ins + e_ins > 32767)
+		return wtz_fail(WTZ_E_ARG, "%s: gap opening costs must be >= 0, gap extension costs >= 1 and open + extend <= 32767", who);
+	S->M = c->P.M; S->X = c->P.X; S->o_del = o_del; S->e_del = e_del; S->o_ins = o_ins; S->e_ins = e_ins; S->zdrop = zdrop;
+	return WTZ_OK;
+}
+/* problem i of a K-kext launch from its two views, or WTZ_E_ARG (the LIMIT of include/wtzmo_hip.h): the band width after the clamp of ksw.c:403-408 and the
+ * diagonals the band can reach, which decide the kernel instantiation */
+static int kext_plan(const wtz_ctx *c, const std::vector<uint64_t> &h_off, const wtz_dp_problem_t &p, uint32_t i, const wtz_kextsc_t &S, int32_t end_bonus, wtz_kextprob_t *d){
+	CHK(dp_problem_views(c, h_off, p, i, false, WTZ_KEXT_MAXLEN, &d->q, &d->t));
+	if(p.W < 0 || p.W > WTZ_KEXT_MAXW) return wtz_fail(WTZ_E_ARG, "problem %u: band width %d outside [0, %d]", i, p.W, WTZ_KEXT_MAXW);
+	const int32_t h0 = p.init_score < 0 ? 0 : p.init_score;
+	if((int64_t)h0 + (int64_t)p.q_len * S.M > (1 << 30)) return wtz_fail(WTZ_E_ARG, "problem %u: start score + q_len * M beyond 2^30", i);
+	if(end_bonus < -(1 << 30) || end_bonus > (1 << 30)) return wtz_fail(WTZ_E_ARG, "problem %u: end bonus beyond 2^30 in magnitude", i);
+	int32_t w = p.W;
+	int32_t max_ins = (int32_t)((double)((int64_t)p.q_len * S.M + end_bonus - S.o_ins) / S.e_ins + 1.); max_ins = max_ins > 1 ? max_ins : 1; w = w < max_ins ? w : max_ins;
+	int32_t max_del = (int32_t)((double)((int64_t)p.q_len * S.M + end_bonus - S.o_del) / S.e_del + 1.); max_del = max_del > 1 ? max_del : 1; w = w < max_del ? w : max_del;
+	d->qlen = p.q_len; d->tlen = p.t_len; d->h0 = h0; d->w = w; d->dlo = w < p.t_len - 1 ? w : p.t_len - 1;
+	return WTZ_OK;
+}
+static int32_t kext_slots(const wtz_kextprob_t &d){ return d.dlo + (d.w < d.qlen - 1 ? d.w : d.qlen - 1) + 1; }
+
+#ifdef WTZ_EMUL
+template<int C> static void kext_emul(const wtz_kextprob_t *pr, const uint32_t *order, uint32_t n, const wtz_kextsc_t &S, wtz_kextres_t *res){
+	for(uint32_t b = 0; b < n; b++) wtz_kext_problem<C>(pr[order[b]], S, res[order[b]]);
+}
+#define KEXT_LAUNCH(C) kext_emul<C>(d_pr, d_order + b0, b1 - b0, S, d_res)
+#else
+#define KEXT_LAUNCH(C) WTZ_LAUNCH(wtz_kernel_kext<C>, b1 - b0, 64, 0, g_stream, (const wtz_kextprob_t*)d_pr, (const uint32_t*)(d_order + b0), b1 - b0, S, d_res)
+#endif
+/* THE launch path of K-kext: the problems of one score setting, one launch per kernel instantiation present, one wavefront per problem, largest first.
+ * hr[i], form[i]: result and slots per lane of problem i.  Counts into ms_kext / n_kext / cells_kext. */
+static int kext_run(wtz_ctx *c, const std::vector<wtz_kextprob_t> &hp, const wtz_kextsc_t &S, std::vector<wtz_kextres_t> &hr, std::vector<uint32_t> &form){
+	const uint32_t n = (uint32_t)hp.size();
+	hr.resize(n); form.resize(n);
+	if(n == 0) return WTZ_OK;
+	wtz_arena_scope launch_scope(&c->arena);      /* the buffers of this launch group go back when it returns (scopes nest) */
+	std::vector<uint32_t> order(n);
+	for(uint32_t i = 0; i < n; i++){ order[i] = i; form[i] = (uint32_t)wtz_kext_form(kext_slots(hp[i])); }
+	std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b){
+		if(form[a] != form[b]) return form[a] > form[b];
+		return (uint64_t)hp[a].tlen * (uint64_t)kext_slots(hp[a]) > (uint64_t)hp[b].tlen * (uint64_t)kext_slots(hp[b]); });
+	wtz_kextprob_t *d_pr = NULL; uint32_t *d_order = NULL; wtz_kextres_t *d_res = NULL;
+	CHK(dev_alloc((void**)&d_pr, (size_t)n * sizeof(wtz_kextprob_t))); CHK(dev_h2d(d_pr, hp.data(), (size_t)n * sizeof(wtz_kextprob_t)));
+	CHK(dev_alloc((void**)&d_order, (size_t)n * 4)); CHK(dev_h2d(d_order, order.data(), (size_t)n * 4));
+	CHK(dev_alloc((void**)&d_res, (size_t)n * sizeof(wtz_kextres_t))); CHK(dev_set(d_res, 0, (size_t)n * sizeof(wtz_kextres_t)));
+	wtz_timer tm; tm.start();
+	for(uint32_t b0 = 0, b1; b0 < n; b0 = b1){
+		const uint32_t C = form[order[b0]];
+		for(b1 = b0 + 1; b1 < n && form[order[b1]] == C; b1++){}
+		switch(C){
+			case 1: KEXT_LAUNCH(1); break;
+			case 2: KEXT_LAUNCH(2); break;
+			case 4: KEXT_LAUNCH(4); break;
+			case 8: KEXT_LAUNCH(8); break;
+			case 16: KEXT_LAUNCH(16); break;
+			default: KEXT_LAUNCH(32); break;
+		}
+	}
+	CHK(dev_sync());
+	c->cnt.ms_kext += tm.stop();
+	CHK(dev_d2h(hr.data(), d_res, (size_t)n * sizeof(wtz_kextres_t)));
+	for(uint32_t i = 0; i < n; i++) c->cnt.cells_kext += hr[i].cells;
+	c->cnt.n_kext += n;
+	return WTZ_OK;
+}
+#undef KEXT_LAUNCH
+/* the main pool goes back empty, as after wtz_local_batch */
+static int kext_leave(wtz_ctx *c, const char *who){
+	CHK(pool_check(c, who));
+	CHK(pool_reset(c));
+	c->main_used_call = 0;
+	return WTZ_OK;
+}
+
+/* ksw_extend2 (ksw.c:381-478) for n independent problems on views of the uploaded reads: K-kext (wtz_sw_kext.h) */
+extern "C" int wtz_kext_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32_t n, int32_t o_del, int32_t e_del, int32_t o_ins, int32_t e_ins, int32_t end_bonus, int32_t zdrop, wtz_kext_result_t *out){
+	if(!c || !c->bits) return wtz_fail(WTZ_E_ARG, "reads not uploaded");
+	if(n == 0) return WTZ_OK;
+	if(!pr || !out) return wtz_fail(WTZ_E_ARG, "null argument");
+	if(n > 0x7FFFFFFFu) return wtz_fail(WTZ_E_ARG, "wtz_kext_batch: more than 2^31 - 1 problems in one call");
+	wtz_kextsc_t S; CHK(kext_scores(c, "wtz_kext_batch", o_del, e_del, o_ins, e_ins, zdrop, &S));
+	CTX_ENTER(c);
+	CHK(pool_reset(c));
+	std::vector<uint64_t> h_off(c->n_reads);
+	CHK(dev_d2h(h_off.data(), c->rdoff, (size_t)c->n_reads * 8));
+	std::vector<wtz_kextprob_t> hp(n);
+	for(uint32_t i = 0; i < n; i++) CHK(kext_plan(c, h_off, pr[i], i, S, end_bonus, &hp[i]));
+	std::vector<wtz_kextres_t> hr; std::vector<uint32_t> form;
+	CHK(kext_run(c, hp, S, hr, form));
+	for(uint32_t i = 0; i < n; i++){
+		wtz_kext_result_t o; memset(&o, 0, sizeof o);
+		o.score = hr[i].score; o.qle = hr[i].qle; o.tle = hr[i].tle; o.gtle = hr[i].gtle; o.gscore = hr[i].gscore; o.max_off = hr[i].max_off;
+		o.form_used = form[i]; o.rows = hr[i].rows; o.cells = hr[i].cells;
+		out[i] = o;
+	}
+	return kext_leave(c, "wtz_kext_batch");
+}
+
+/* kswx_align_no_stat (kswx.h:1504-1511): the local hit of wtz_local_batch, then kswx_extend_core (kswx.h:1386-1441) as two stages of K-kext launches.
+ * side 0 = left (the reversed prefixes in front of the hit), 1 = right; role 0 = the problem's target is ksw_extend2's target (rows), 1 = its query is. */
+extern "C" int wtz_align_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32_t n, int32_t w, int32_t I, int32_t D, int32_t E, int32_t T, wtz_align_result_t *out){
+	if(!c || !c->bits) return wtz_fail(WTZ_E_ARG, "reads not uploaded");
+	if(n == 0) return WTZ_OK;
+	if(!pr || !out) return wtz_fail(WTZ_E_ARG, "null argument");
+	if(I > 0 || D > 0 || E > -1 || I < -32767 || D < -32767 || E < -32767 || T < -(1 << 30)) return wtz_fail(WTZ_E_ARG, "wtz_align_batch: I and D must be <= 0 and E <= -1 (costs as negative numbers)");
+	if(w < 0 || w > WTZ_KEXT_MAXW) return wtz_fail(WTZ_E_ARG, "wtz_align_batch: band width %d outside [0, %d]", w, WTZ_KEXT_MAXW);
+	wtz_kextsc_t SR[2];      /* by role: kswx.h:1396 / 1422 and, with the opening costs exchanged, kswx.h:1407 / 1431 */
+	CHK(kext_scores(c, "wtz_align_batch", -D, -E, -I, -E, -1, &SR[0]));
+	CHK(kext_scores(c, "wtz_align_batch", -I, -E, -D, -E, -1, &SR[1]));
+	CTX_ENTER(c);
+	/* stage 1; its own checks (1 <= q_len, t_len <= 65535, the views) come before its launch, and nothing else has run by then */
+	std::vector<wtz_local_result_t> loc(n);
+	CHK(wtz_local_batch(c, pr, n, -D, -E, -I, -E, loc.data()));
+	for(uint32_t i = 0; i < n; i++){
+		wtz_align_result_t o; memset(&o, 0, sizeof o);
+		const wtz_local_result_t &l = loc[i];
+		if(!(l.qb <= -1 || l.tb <= -1 || l.qe <= -1 || l.te <= -1)){
+			o.found = 1; o.score = o.local_score = l.score; o.tb = o.local_tb = l.tb; o.qb = o.local_qb = l.qb; o.te = o.local_te = l.te + 1; o.qe = o.local_qe = l.qe + 1;
+		}
+		out[i] = o;
+	}
+	if(T >= 0) return WTZ_OK;
+	CHK(pool_reset(c));
+	std::vector<uint64_t> h_off(c->n_reads);
+	CHK(dev_d2h(h_off.data(), c->rdoff, (size_t)c->n_reads * 8));
+	for(int side = 0; side < 2; side++){
+		std::vector<wtz_kextprob_t> hp[2]; std::vector<uint32_t> who[2];
+		for(uint32_t i = 0; i < n; i++){
+			const wtz_align_result_t &o = out[i];
+			if(!o.found) continue;
+			const wtz_dp_problem_t &p = pr[i];
+			const int32_t remq = side == 0 ? o.qb : p.q_len - o.qe, remt = side == 0 ? o.tb : p.t_len - o.te;
+			if(remq == 0 || remt == 0) continue;                                   /* kswx.h:1391, 1418 */
+			const int role = remt >= remq ? 0 : 1;
+			const int32_t cols = role == 0 ? remq : remt, other = role == 0 ? remt : remq;
+			const int32_t nrow = cols + w > other ? other : cols + w;              /* the row side is cut to the column side + w */
+			/* the two remaining sides as views of the problem's views: from the hit outwards */
+			wtz_dp_problem_t e = p;
+			const int32_t qat = side == 0 ? o.qb - 1 : o.qe, tat = side == 0 ? o.tb - 1 : o.te, dir = side == 0 ? -1 : 1;
+			const int32_t qf = p.q_from + p.q_strand * qat, tf = p.t_from + p.t_strand * tat, qs = p.q_strand * dir, ts = p.t_strand * dir;
+			if(role == 0){ e.q_from = qf; e.q_strand = qs; e.q_len = cols; e.t_from = tf; e.t_strand = ts; e.t_len = nrow; }
+			else { e.q_read = p.t_read; e.q_rev = p.t_rev; e.q_from = tf; e.q_strand = ts; e.q_len = cols; e.t_read = p.q_read; e.t_rev = p.q_rev; e.t_from = qf; e.t_strand = qs; e.t_len = nrow; }
+			e.init_score = o.score; e.W = w;
+			wtz_kextprob_t d; CHK(kext_plan(c, h_off, e, i, SR[role], -T, &d));
+			hp[role].push_back(d); who[role].push_back(i);
+		}
+		for(int role = 0; role < 2; role++){
+			std::vector<wtz_kextres_t> hr; std::vector<uint32_t> form;
+			CHK(kext_run(c, hp[role], SR[role], hr, form));
+			for(size_t k = 0; k < hr.size(); k++){
+				wtz_align_result_t &o = out[who[role][k]];
+				const wtz_dp_problem_t &p = pr[who[role][k]];
+				const wtz_kextres_t &x = hr[k];
+				const bool clip = x.gscore <= 0 || x.gscore <= x.score + T;        /* kswx.h:1398: the best cell, not the end of the column side */
+				/* columns / rows taken: (qle, tle), or everything that was left of the column side and gtle rows */
+				const int32_t dcol = clip ? x.qle : -1, drow = clip ? x.tle : x.gtle;
+				int32_t &qend = side == 0 ? o.qb : o.qe, &tend = side == 0 ? o.tb : o.te;
+				const int32_t qlim = side == 0 ? 0 : p.q_len, tlim = side == 0 ? 0 : p.t_len, sg = side == 0 ? -1 : 1;
+				if(role == 0){ qend = dcol < 0 ? qlim : qend + sg * dcol; tend += sg * drow; }
+				else { tend = dcol < 0 ? tlim : tend + sg * dcol; qend += sg * drow; }
+				o.score = clip ? x.score : x.gscore;
+			}
+		}
+	}
+	return kext_leave(c, "wtz_align_batch");
 }
 
 #include "wtz_testdp.h"

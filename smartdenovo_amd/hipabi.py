@@ -17,7 +17,7 @@ SYMBOLS = [
     "wtz_last_error", "wtz_device_count", "wtz_device_memory", "wtz_ctx_create", "wtz_ctx_destroy", "wtz_ctx_clone", "wtz_upload_reads",
     "wtz_index_build", "wtz_zindex_build", "wtz_candidates", "wtz_candidates_begin", "wtz_candidates_end", "wtz_batch_begin", "wtz_pairs_seed",
     "wtz_pairs_windows", "wtz_pairs_align", "wtz_fetch_cigars", "wtz_fetch_cigar_text", "wtz_fetch_cigar_text_begin", "wtz_fetch_cigar_text_end", "wtz_cigar_text_device", "wtz_host_alloc", "wtz_host_free", "wtz_get_counters", "wtz_reset_counters",
-    "wtz_test_dp", "wtz_extend_batch", "wtz_local_batch", "wtz_pool_info", "wtz_pool_failure_kind",
+    "wtz_test_dp", "wtz_extend_batch", "wtz_local_batch", "wtz_kext_batch", "wtz_align_batch", "wtz_pool_info", "wtz_pool_failure_kind",
     "wtz_index_count", "wtz_index_counts_fetch", "wtz_index_finish", "wtz_candidate_groups_begin", "wtz_candidate_groups_end", "wtz_candidate_groups_fetch", "wtz_cand_tail_host", "wtz_zindex_build_subset", "wtz_zindex_build_queries", "wtz_upload_reads_ascii", "wtz_fetch_read_bits", "wtz_append_revcomp_views",
 ]
 
@@ -64,6 +64,11 @@ DP_RESULT = np.dtype([("score", "<i4"), ("tb", "<i4"), ("te", "<i4"), ("qb", "<i
 DP_SHIFT, DP_FIXED, DP_GLOBAL = 0, 1, 2
 LOCAL_RESULT = np.dtype([("score", "<i4"), ("te", "<i4"), ("qe", "<i4"), ("tb", "<i4"), ("qb", "<i4"), ("form_used", "<u4"), ("cells", "<u8")])
 LOCAL_MAXLEN = 65535      # rows / columns of one wtz_local_batch problem (include/wtzmo_hip.h)
+KEXT_RESULT = np.dtype([("score", "<i4"), ("qle", "<i4"), ("tle", "<i4"), ("gtle", "<i4"), ("gscore", "<i4"), ("max_off", "<i4"),
+                        ("form_used", "<u4"), ("rows", "<u4"), ("cells", "<u8")])
+KEXT_MAXW = 1023          # band half-width of one wtz_kext_batch problem (WTZ_KEXT_MAXW)
+KEXT_MAXLEN = 0xFFFFF     # its rows / columns (WTZ_KEXT_MAXLEN)
+ALIGN_RESULT = np.dtype([(n, "<i4") for n in ("found", "score", "tb", "te", "qb", "qe", "local_score", "local_tb", "local_te", "local_qb", "local_qe")])
 
 
 class Counters(C.Structure):
@@ -72,7 +77,8 @@ class Counters(C.Structure):
                                           "cells_global", "bytes_seed_algo", "pool_peak")] + \
                [("ms_ext", C.c_double), ("n_extjobs", C.c_uint64), ("ms_gap", C.c_double), ("bytes_zmer_algo", C.c_uint64),
                 ("ms_ingest", C.c_double), ("bytes_ingest_algo", C.c_uint64),
-                ("ms_local", C.c_double), ("n_local", C.c_uint64), ("cells_local", C.c_uint64)]
+                ("ms_local", C.c_double), ("n_local", C.c_uint64), ("cells_local", C.c_uint64),
+                ("ms_kext", C.c_double), ("n_kext", C.c_uint64), ("cells_kext", C.c_uint64)]
 
 
 def load(path: str | None = None) -> C.CDLL:
@@ -224,6 +230,22 @@ class Context:
         out = np.zeros(problems.size, dtype=LOCAL_RESULT)
         self.lib.wtz_local_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         self._chk(self.lib.wtz_local_batch(self.h, problems.ctypes.data, problems.size, o_del, e_del, o_ins, e_ins, out.ctypes.data))
+        return out
+
+    def kext_batch(self, problems, o_del, e_del, o_ins, e_ins, end_bonus, zdrop):
+        """ksw_extend2 per problem (wtz_kext_batch): q_* = its query (columns), t_* = its target (rows), init_score = h0, W = w."""
+        problems = np.ascontiguousarray(problems, dtype=DP_PROBLEM)
+        out = np.zeros(problems.size, dtype=KEXT_RESULT)
+        self.lib.wtz_kext_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_int32] * 6 + [C.c_void_p]
+        self._chk(self.lib.wtz_kext_batch(self.h, problems.ctypes.data, problems.size, o_del, e_del, o_ins, e_ins, end_bonus, zdrop, out.ctypes.data))
+        return out
+
+    def align_batch(self, problems, w, I, D, E, T):
+        """kswx_align_no_stat per problem (wtz_align_batch): the local hit extended to both sides; I, D, E, T as negative costs."""
+        problems = np.ascontiguousarray(problems, dtype=DP_PROBLEM)
+        out = np.zeros(problems.size, dtype=ALIGN_RESULT)
+        self.lib.wtz_align_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_int32] * 5 + [C.c_void_p]
+        self._chk(self.lib.wtz_align_batch(self.h, problems.ctypes.data, problems.size, w, I, D, E, T, out.ctypes.data))
         return out
 
     def counters(self) -> Counters:
