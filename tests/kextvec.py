@@ -1,5 +1,5 @@
-"""Shared pieces of the ksw_extend2 / kswx_align_no_stat tests (tests/test_kext_cpu.py, tests/test_gpu_kext.py) and of the generator of their vectors
-(tests/golden/make_kext_vectors.py).
+"""Shared pieces of the ksw_extend2 / kswx_align_no_stat tests (tests/test_kext_cpu.py, tests/test_gpu_kext.py, tests/test_gpu_kext_wide.py) and of the
+generators of their vectors (tests/golden/make_kext_vectors.py, tests/golden/make_kext_wide_vectors.py).
 
 Two functions of the reference are called live through oracle/_ref/libref_shim.so: ksw_extend2 (ksw.c:381-478) and, through localvec, ksw_align2
 (ksw.c:344-366).  Both are exported from the reference's ksw.c as it is.
@@ -24,6 +24,8 @@ from smartdenovo_amd import hipabi
 ROOT = lv.ROOT
 SHIM = lv.SHIM
 VECTORS = os.path.join(ROOT, "tests", "golden", "kext_vectors.npz")
+WIDE_VECTORS = os.path.join(ROOT, "tests", "golden", "kext_wide_vectors.npz")      # tests/golden/make_kext_wide_vectors.py
+FORMS = (1, 2, 4, 8, 16, 32)                                                        # slots per lane of the six kernel instantiations
 FIELDS = ("score", "qle", "tle", "gtle", "gscore", "max_off")
 CHAIN_FIELDS = ("found", "score", "tb", "te", "qb", "qe")
 GAPS = ((3, 1, 3, 1), (2, 1, 3, 1), (3, 1, 2, 1), (4, 2, 4, 2))      # (o_del, e_del, o_ins, e_ins)
@@ -137,8 +139,36 @@ def py_extend(q, t, M, X, gaps, w, end_bonus, zdrop, h0, trim=True):
     return (mx, max_j + 1, max_i + 1, max_ie + 1, gscore, max_off), stop, rows, cells
 
 
-def ref_chain(q, t, M, X, w, I, D, E, T, extend=ref_extend, align=lv.ref_align):
-    """kswx_align_no_stat (kswx.h:1504-1511) restated around the live ksw_align2 / ksw_extend2: ((found, score, tb, te, qb, qe), flags, local five)"""
+def clamped_w(qlen, M, X, gaps, w, end_bonus):
+    """the band half-width after the clamp of ksw.c:403-408"""
+    mxs = max(M, X)
+    w = min(w, max(1, int((qlen * mxs + end_bonus - gaps[2]) / gaps[3] + 1.)))
+    return min(w, max(1, int((qlen * mxs + end_bonus - gaps[0]) / gaps[1] + 1.)))
+
+
+def slots_of(qlen, tlen, M, X, gaps, w, end_bonus):
+    """live diagonals of a problem as the host plans them (kext_plan / kext_slots of wtz_lib_batch.h): min(w, tlen - 1) + min(w, qlen - 1) + 1 of the clamped w"""
+    w = clamped_w(qlen, M, X, gaps, w, end_bonus)
+    return min(w, tlen - 1) + min(w, qlen - 1) + 1
+
+
+def form_of(slots):
+    """wtz_kext_form: slots per lane of the instantiation that takes a band of `slots` diagonals"""
+    c = 1
+    while c < 32 and 64 * c < slots:
+        c <<= 1
+    return c
+
+
+def ref_chain(q, t, M, X, w, I, D, E, T, extend=ref_extend, align=lv.ref_align, record=None):
+    """kswx_align_no_stat (kswx.h:1504-1511) restated around the live ksw_align2 / ksw_extend2: ((found, score, tb, te, qb, qe), flags, local five).
+    record: a list that receives (side, role, arguments handed to `extend`) of every extension stage that ran (side 0 = left, role 1 = query is the rows)"""
+    if record is not None:
+        inner, stage = extend, [0, 0]
+
+        def extend(*a):
+            record.append((stage[0], stage[1], a))
+            return inner(*a)
     q = np.asarray(q, dtype=np.uint8)
     t = np.asarray(t, dtype=np.uint8)
     qlen, tlen = q.size, t.size
@@ -155,6 +185,8 @@ def ref_chain(q, t, M, X, w, I, D, E, T, extend=ref_extend, align=lv.ref_align):
             flags |= F_LEFT_SKIP
         elif tb >= qb:                                                        # kswx.h:1392-1402
             flags |= F_LEFT_RAN
+            if record is not None:
+                stage[:] = [0, 0]
             y1, y2 = (tb if qb + w > tb else qb + w), qb
             sc, x2, x1, x3, gs, _ = extend(q[qb - y2:qb][::-1], t[tb - y1:tb][::-1], M, X, g_t, w, -T, -1, score)
             if gs <= 0 or gs <= sc + T:
@@ -164,6 +196,8 @@ def ref_chain(q, t, M, X, w, I, D, E, T, extend=ref_extend, align=lv.ref_align):
                 flags |= F_LEFT_GSCORE
         else:                                                                 # kswx.h:1403-1413
             flags |= F_LEFT_RAN | F_LEFT_ROLE1
+            if record is not None:
+                stage[:] = [0, 1]
             y1, y2 = tb, (qb if tb + w > qb else tb + w)
             sc, x1, x2, x3, gs, _ = extend(t[tb - y1:tb][::-1], q[qb - y2:qb][::-1], M, X, g_q, w, -T, -1, score)
             if gs <= 0 or gs <= sc + T:
@@ -175,6 +209,8 @@ def ref_chain(q, t, M, X, w, I, D, E, T, extend=ref_extend, align=lv.ref_align):
             flags |= F_RIGHT_SKIP
         elif tlen - te >= qlen - qe:                                          # kswx.h:1419-1427
             flags |= F_RIGHT_RAN
+            if record is not None:
+                stage[:] = [1, 0]
             y1, y2 = ((tlen - te) if qlen - qe + w > tlen - te else qlen - qe + w), qlen - qe
             sc, x2, x1, x3, gs, _ = extend(q[qe:qe + y2], t[te:te + y1], M, X, g_t, w, -T, -1, score)
             if gs <= 0 or gs <= sc + T:
@@ -184,6 +220,8 @@ def ref_chain(q, t, M, X, w, I, D, E, T, extend=ref_extend, align=lv.ref_align):
                 flags |= F_RIGHT_GSCORE
         else:                                                                 # kswx.h:1428-1436
             flags |= F_RIGHT_RAN | F_RIGHT_ROLE1
+            if record is not None:
+                stage[:] = [1, 1]
             y1, y2 = tlen - te, ((qlen - qe) if tlen - te + w > qlen - qe else tlen - te + w)
             sc, x1, x2, x3, gs, _ = extend(t[te:te + y1], q[qe:qe + y2], M, X, g_q, w, -T, -1, score)
             if gs <= 0 or gs <= sc + T:
@@ -194,8 +232,8 @@ def ref_chain(q, t, M, X, w, I, D, E, T, extend=ref_extend, align=lv.ref_align):
     return (1, score, tb, te, qb, qe), flags, local
 
 
-def load_vectors():
-    z = np.load(VECTORS)
+def load_vectors(path=None):
+    z = np.load(path or VECTORS)
     return {k: z[k] for k in z.files}
 
 
@@ -204,6 +242,9 @@ def problems_of(v):
     pr = np.zeros(len(v["f_q_read"]), dtype=hipabi.DP_PROBLEM)
     for f in ("q_read", "t_read", "q_from", "t_from", "q_strand", "t_strand", "q_len", "t_len", "init_score", "W"):
         pr[f] = v["f_" + f]
+    for f in ("q_rev", "t_rev"):      # kext_vectors.npz has neither: whole reads as uploaded
+        if "f_" + f in v:
+            pr[f] = v["f_" + f]
     return pr
 
 

@@ -2,7 +2,8 @@
 (tests/emul: one lane that holds all 64 * C band slots), is the CPU restatement of the reference's ksw_extend2 (ksw.c:381-478).  It must give the six ints
 of the reference
   - for every problem of tests/golden/kext_vectors.npz (dumped from the reference routine by tests/golden/make_kext_vectors.py), and
-  - where oracle/_ref/libref_shim.so exists, for 2 000 fresh seeded pairs against the routine called live: mismatches allowed, 0.
+  - for every problem of tests/golden/kext_wide_vectors.npz (the wide forms, the slot counts at the form edges, views, long problems), and
+  - where oracle/_ref/libref_shim.so exists, for 2 000 + 200 fresh seeded pairs against the routine called live: mismatches allowed, 0.
 The chain wtz_align_batch (kswx_align_no_stat, kswx.h:1504-1511) is compared with the chain table of the same file and, where the shim exists, with
 kextvec.ref_chain run live on 300 fresh pairs (see tests/kextvec.py for what that restatement pins and what the reference's compiled code pins)."""
 import os
@@ -114,12 +115,8 @@ def _mutate(rng, s, rate):
     return np.array(out if out else [0], dtype=np.uint8)
 
 
-@needs_shim
-def test_restatement_equals_live_ksw_extend2_on_fresh_pairs(emul_lib):
-    """2 000 pairs, lengths 1-300 (a quarter unrelated, the rest mutated at 12 / 25 / 35 % with deletion runs, half of those followed by unrelated
-    sequence, a third over a two-letter alphabet), w, h0, zdrop, end_bonus and the gap costs drawn from the lists of kextvec.  Mismatches allowed: 0."""
-    rng = np.random.default_rng(19)
-    N = 2000
+def _fresh_pairs_narrow(rng, N):
+    """lengths 1-300, w in {3, 10, 40, 800}"""
     seqs, par = [], []
     for n in range(N):
         a = rng.integers(0, 4 if n % 3 else 2, int(rng.integers(1, 301))).astype(np.uint8)
@@ -132,19 +129,59 @@ def test_restatement_equals_live_ksw_extend2_on_fresh_pairs(emul_lib):
             b = b[:300]
         seqs += [a, b]
         par.append((int(rng.integers(4)), int(rng.choice(kv.END_BONUS)), int(rng.choice(kv.ZDROPS)), int(rng.choice((3, 10, 40, 800))), int(rng.choice(kv.H0S))))
-    par = np.array(par)
-    words, offs, lens = hipabi.pack_reads(seqs)
-    ctx = lv.make_context(words, offs, lens, 2, -5, lib_path=emul_lib)
-    try:
-        pr = lv.whole_read_problems(np.arange(0, 2 * N, 2), np.arange(1, 2 * N, 2), lens)
-        pr["W"], pr["init_score"] = par[:, 3], par[:, 4]
-        got = kv.six(kv.run_by_group(ctx, pr, par[:, 0], par[:, 1], par[:, 2]))
-    finally:
-        ctx.close()
-    ref = np.array([kv.ref_extend(seqs[2 * n], seqs[2 * n + 1], 2, -5, kv.GAPS[par[n, 0]], int(par[n, 3]), int(par[n, 1]), int(par[n, 2]), int(par[n, 4])) for n in range(N)], dtype=np.int64)
-    bad = np.nonzero((got != ref).any(axis=1))[0]
-    assert bad.size == 0, [(int(b), par[b].tolist(), got[b].tolist(), ref[b].tolist()) for b in bad[:8]]
-    assert (ref[:, 4] > ref[:, 0] - 100).sum() > N // 10 and (ref[:, 2] > 20).sum() > N // 3      # the set is not trivially empty of extensions
+    return seqs, np.array(par)
+
+
+def _fresh_pairs_wide(rng, N):
+    """sides of 300-2 200, w in {300, 512, 800, 1023}, h0 in {0, 1, 30, 400, 5000}; the mutated copies that are cut off go on with unrelated sequence"""
+    seqs, par = [], []
+    for n in range(N):
+        k = 4 if n % 3 else 2
+        a = rng.integers(0, k, int(rng.integers(300, 2201))).astype(np.uint8)
+        if n % 4 == 0:
+            b = rng.integers(0, k, int(rng.integers(300, 2201))).astype(np.uint8)
+        else:
+            b = _mutate(rng, a, (0.12, 0.25, 0.35)[n % 3]) % k
+            if n & 1:
+                b = np.concatenate([b[:int(rng.integers(75, b.size + 1))], rng.integers(0, k, int(rng.integers(150, 1100))).astype(np.uint8)])
+            b = np.concatenate([b, rng.integers(0, k, max(0, 300 - b.size)).astype(np.uint8)])[:2200]
+        seqs += [a, b.astype(np.uint8)]
+        par.append((int(rng.integers(4)), int(rng.choice(kv.END_BONUS)), int(rng.choice(kv.ZDROPS)), int(rng.choice((300, 512, 800, 1023))), int(rng.choice((0, 1, 30, 400, 5000)))))
+    return seqs, np.array(par)
+
+
+@needs_shim
+def test_restatement_equals_live_ksw_extend2_on_fresh_pairs(emul_lib):
+    """narrow: 2 000 pairs, lengths 1-300 (a quarter unrelated, the rest mutated at 12 / 25 / 35 % with deletion runs, half of those followed by unrelated
+    sequence, a third over a two-letter alphabet), w, h0, zdrop, end_bonus and the gap costs drawn from the lists of kextvec.
+    wide: 200 pairs drawn the same way with sides of 300-2 200 and w up to 1 023; sixteen and thirty-two slots per lane occur at least 40 times each.
+    Mismatches allowed: 0."""
+    for which in ("narrow", "wide"):
+        if which == "narrow":
+            N = 2000
+            seqs, par = _fresh_pairs_narrow(np.random.default_rng(19), N)
+        else:
+            N = 200
+            seqs, par = _fresh_pairs_wide(np.random.default_rng(29), N)
+        words, offs, lens = hipabi.pack_reads(seqs)
+        ctx = lv.make_context(words, offs, lens, 2, -5, lib_path=emul_lib)
+        try:
+            pr = lv.whole_read_problems(np.arange(0, 2 * N, 2), np.arange(1, 2 * N, 2), lens)
+            pr["W"], pr["init_score"] = par[:, 3], par[:, 4]
+            out = kv.run_by_group(ctx, pr, par[:, 0], par[:, 1], par[:, 2])
+            got = kv.six(out)
+        finally:
+            ctx.close()
+        ref = np.array([kv.ref_extend(seqs[2 * n], seqs[2 * n + 1], 2, -5, kv.GAPS[par[n, 0]], int(par[n, 3]), int(par[n, 1]), int(par[n, 2]), int(par[n, 4])) for n in range(N)], dtype=np.int64)
+        bad = np.nonzero((got != ref).any(axis=1))[0]
+        assert bad.size == 0, [(which, int(b), par[b].tolist(), got[b].tolist(), ref[b].tolist()) for b in bad[:8]]
+        if which == "narrow":
+            assert (ref[:, 4] > ref[:, 0] - 100).sum() > N // 10 and (ref[:, 2] > 20).sum() > N // 3      # the set is not trivially empty of extensions
+        else:
+            form = [kv.form_of(kv.slots_of(seqs[2 * n].size, seqs[2 * n + 1].size, 2, -5, kv.GAPS[par[n, 0]], int(par[n, 3]), int(par[n, 1]))) for n in range(N)]
+            assert (out["form_used"] == form).all()
+            assert form.count(16) >= 40 and form.count(32) >= 40, (form.count(16), form.count(32))
+            assert (ref[:, 2] > 200).sum() > N // 3
 
 
 def test_chain_equals_the_chain_table(vctx, V):
@@ -255,3 +292,113 @@ def test_limits_and_bad_arguments_are_argument_errors_and_the_context_survives(e
         assert lv.pool_info(ctx).main_used == 0
     finally:
         ctx.close()
+
+
+# ---- tests/golden/kext_wide_vectors.npz: the wide forms with every exit, the slot counts at the form edges, views, long problems (make_kext_wide_vectors.py) ----
+EDGE_S = tuple(64 * c + d for c in (1, 2, 4, 8, 16) for d in (-1, 0, 1)) + (2047,)
+
+
+@pytest.fixture(scope="module")
+def W():
+    return kv.load_vectors(kv.WIDE_VECTORS)
+
+
+@pytest.fixture(scope="module")
+def wctx(emul_lib, W):
+    c = lv.make_context(W["words"], W["offs"], W["lens"], int(W["M"]), int(W["X"]), lib_path=emul_lib)
+    yield c
+    c.close()
+
+
+def test_wide_vector_file_meets_the_conditions_it_was_made_for(W):
+    """recomputed from the file: per kernel form at least 3 problems of every exit and branch, at least 4 per slot count at a form edge, the views"""
+    names = [str(x) for x in W["f_names"]]
+    n = len(names)
+    e = W["f_expect"].astype(np.int64)
+    assert len(set(names)) == n and os.path.getsize(kv.WIDE_VECTORS) < (1 << 19)
+    assert int(W["M"]) == 2 and int(W["X"]) == -5
+    assert set(int(x) for x in W["f_init_score"]) <= set(kv.H0S) and set(int(x) for x in W["f_zdrop"]) == set(kv.ZDROPS)
+    assert set(int(x) for x in W["f_end_bonus"]) == set(kv.END_BONUS) and set(int(x) for x in W["f_gap"]) == {0, 1, 2, 3}
+    slots = np.array([kv.slots_of(int(W["f_q_len"][i]), int(W["f_t_len"][i]), 2, -5, kv.GAPS[W["f_gap"][i]], int(W["f_W"][i]), int(W["f_end_bonus"][i])) for i in range(n)])
+    form = np.array([kv.form_of(int(s)) for s in slots])
+    assert (slots == W["f_slots"]).all() and (form == W["f_form"]).all()
+    stop = W["f_stop"]
+    for c in kv.FORMS:
+        f = form == c
+        for what, sel in (("last row", stop == kv.STOP_END), ("m == 0", stop == kv.STOP_M0), ("z-drop", stop == kv.STOP_ZDROP), ("trim matters", W["f_trim"] != 0),
+                          ("gscore == -1", e[:, 4] == -1), ("gscore > score - 100", e[:, 4] > e[:, 0] - 100)):
+            assert (f & sel).sum() >= 3, (c, what)
+    for S in EDGE_S:
+        i = [k for k in range(n) if slots[k] == S]
+        assert len(i) >= 4, S
+        kinds = set(names[k].split("_", 2)[2] for k in i if names[k].startswith("edge_S%d_" % S))
+        assert kinds == {"copy", "unrelated", "prefix", "all_A", "copy_short_t", "copy_short_q"}, S
+        w = [kv.clamped_w(int(W["f_q_len"][k]), 2, -5, kv.GAPS[W["f_gap"][k]], int(W["f_W"][k]), int(W["f_end_bonus"][k])) for k in i]
+        if S != 2047:      # 2 * 1023 + 1: no side can be shorter than the widest band
+            assert any(W["f_t_len"][k] - 1 < ww for k, ww in zip(i, w)) and any(W["f_q_len"][k] - 1 < ww for k, ww in zip(i, w)), S
+        else:
+            assert any(W["f_t_len"][k] - 1 == ww for k, ww in zip(i, w)) and any(W["f_q_len"][k] - 1 == ww for k, ww in zip(i, w))
+    view = np.array([k for k in range(n) if names[k].startswith("view_")])
+    assert set(int(x) % 32 for x in W["f_q_from"][view]) == set(range(32)) and set(int(x) % 32 for x in W["f_t_from"][view]) == set(range(32))
+    wide_kinds = set((int(W["f_q_strand"][k]), int(W["f_t_strand"][k]), int(W["f_q_rev"][k]), int(W["f_t_rev"][k])) for k in view if form[k] >= 8)
+    assert len(wide_kinds) == 16                  # the four strand combinations x (no rev, q_rev, t_rev, both), each in a form with C >= 8
+    lens, nreads = W["lens"].astype(np.int64), len(W["lens"])
+
+    def span(k, side):      # first and last base of the view in the read as it was uploaded
+        a = int(W["f_%s_from" % side][k])
+        b = a + int(W["f_%s_strand" % side][k]) * (int(W["f_%s_len" % side][k]) - 1)
+        if W["f_%s_rev" % side][k]:
+            a, b = lens[W["f_%s_read" % side][k]] - 1 - a, lens[W["f_%s_read" % side][k]] - 1 - b
+        return min(a, b), max(a, b)
+    first = [k for k in view if W["f_q_read"][k] == 0 and span(k, "q")[0] == 0]
+    last = [k for k in view if W["f_t_read"][k] == nreads - 1 and span(k, "t")[1] == lens[-1] - 1]
+    assert set(int(W["f_q_strand"][k]) for k in first) == {1, -1}
+    assert set((int(W["f_t_strand"][k]), int(W["f_t_rev"][k])) for k in last) == {(1, 0), (-1, 0), (1, 1)}
+    i = names.index("rows_20000_w40")
+    assert W["f_rows"][i] == 20000 and stop[i] == kv.STOP_END and W["f_W"][i] == 40
+    i = names.index("rows_6000_w1023")
+    assert W["f_rows"][i] > 5000 and form[i] == 32
+    # the chain rows: both roles on both sides in both wide forms, at least twice
+    cf, cs = W["c_flags"].astype(np.int64), W["c_slots"]
+    assert 30 <= len(cf) <= 60 and set(int(x) for x in W["c_w"]) == {800, 1023} and set(int(x) for x in W["c_T"]) == {-100, -30}
+    assert abs(int(W["c_t_rev"].sum()) * 2 - len(cf)) <= 2
+    for side, (ran, role1) in enumerate(((kv.F_LEFT_RAN, kv.F_LEFT_ROLE1), (kv.F_RIGHT_RAN, kv.F_RIGHT_ROLE1))):
+        assert (((cf & ran) != 0) == (cs[:, side] > 0)).all()
+        for role in (0, 1):
+            for c in (16, 32):
+                cnt = sum(1 for k in range(len(cf)) if cf[k] & ran and bool(cf[k] & role1) == bool(role) and kv.form_of(int(cs[k, side])) == c)
+                assert cnt >= 2, (side, role, c)
+
+
+def test_restatement_equals_wide_reference_vectors(wctx, W):
+    pr = kv.problems_of(W)
+    out = kv.run_by_group(wctx, pr, W["f_gap"], W["f_end_bonus"], W["f_zdrop"])
+    got, exp = kv.six(out), W["f_expect"].astype(np.int64)
+    bad = np.nonzero((got != exp).any(axis=1))[0]
+    assert bad.size == 0, [(str(W["f_names"][b]), got[b].tolist(), exp[b].tolist()) for b in bad[:8]]
+    assert (out["rows"] == W["f_rows"]).all() and (out["cells"] == W["f_cells"].astype(np.uint64)).all()
+    assert (out["form_used"] == W["f_form"]).all()
+    assert lv.pool_info(wctx).main_used == 0
+
+
+def test_chain_equals_the_wide_chain_table(wctx, W):
+    pr = kv.chain_problems(W["c_q_read"], W["c_t_read"], W["c_t_rev"], W["lens"])
+    c0 = wctx.counters()
+    out = kv.run_chain_by_group(wctx, pr, W["c_w"], W["c_T"])
+    got, exp = kv.chain_six(out), W["c_expect"].astype(np.int64)
+    bad = np.nonzero((got != exp).any(axis=1))[0]
+    assert bad.size == 0, [(str(W["c_names"][b]), got[b].tolist(), exp[b].tolist()) for b in bad[:8]]
+    loc = np.stack([out[f] for f in ("local_score", "local_tb", "local_te", "local_qb", "local_qe")], axis=1).astype(np.int64)
+    assert (loc == W["c_local"]).all()
+    assert wctx.counters().n_kext - c0.n_kext == (W["c_slots"] > 0).sum()
+    assert lv.pool_info(wctx).main_used == 0
+
+
+def test_kext_problem_stand_alone(tmp_path):
+    """tests/emul/check_kext.cpp: wtz_kext_problem<C> of all six C against a scalar restatement of ksw_extend2 written in that file, on views at both ends of
+    an array allocated to the word"""
+    exe = os.path.join(str(tmp_path), "check_kext")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-DWTZ_EMUL", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "smartdenovo_amd", "csrc"),
+                    "-o", exe, os.path.join(ROOT, "tests", "emul", "check_kext.cpp")], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and " 0 bad" in r.stdout, r.stdout + r.stderr
