@@ -245,7 +245,7 @@ static int hx_set_has(const hx_set_t *s, uint64_t v){
 }
 /* the same probe for a thread that reads while the owner inserts (round 6: the commit's helper threads).  Safe as long as the table does not grow meanwhile
  * (hx_set_reserve in front): a slot goes from empty to a key in one aligned 64-bit store, so a reader sees the key or not yet - callers detect "not yet" by
- * other means (wtzmo_main.c: closed_touch) */
+ * other means (wtzmo_commit.h: closed_touch) */
 static int hx_set_has_racy(const hx_set_t *s, uint64_t v){
 	if(!s->cap) return 0;
 	size_t m = s->cap - 1, i = hx_mix(v) & m;

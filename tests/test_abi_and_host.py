@@ -92,7 +92,7 @@ def test_repeat_rich_window_scans_on_the_pool_workspace(emul_exe, oracle_exe, tm
 
 
 def test_scratch_pool_exhaustion_splits_the_batch(emul_exe, tmp_path):
-    """WTZ_E_POOL path (wtzmo_main.c process_range): a pool too small for the whole batch halves it until it fits; the output
+    """WTZ_E_POOL path (wtzmo_ranges.h range_overflowed): a pool too small for the whole batch halves it until it fits; the output
     is unchanged.  (A task that ran out of scratch once used to go on with a NULL row buffer: wtz_swmem_need is sticky now.)"""
     case = manifest()["cases"]["zmo"]
     out = os.path.join(str(tmp_path), "o.ovl")
@@ -104,6 +104,54 @@ def test_scratch_pool_exhaustion_splits_the_batch(emul_exe, tmp_path):
     # far too small: a loud failure, never a crash or a wrong file
     r = subprocess.run([emul_exe, "-i", os.path.join(ROOT, "tests", "golden", case["input"]), "-fo", out, "--pool-mb", "8"] + case["argv"], capture_output=True)
     assert r.returncode == 1 and b"scratch pool" in r.stderr
+
+
+@pytest.mark.parametrize("env", [{}, {"WTZ_RANGE_OVERLAP": "0"}], ids=["pipelined", "serial"])
+def test_pool_overflow_splits_from_both_callers(env, emul_exe, tmp_path, monkeypatch):
+    """The overflow of a range reached from the pipelined ranges (a helper thread's range came back too large) and from the serial path's own recursion
+    (WTZ_RANGE_OVERLAP=0): both halve the range, say so, and write the golden.  192 MB overflows on both paths."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    case = manifest()["cases"]["zmo"]
+    out = os.path.join(str(tmp_path), "o.ovl")
+    r = subprocess.run([emul_exe, "-i", os.path.join(ROOT, "tests", "golden", case["input"]), "-fo", out, "--pool-mb", "192"] + case["argv"], capture_output=True)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    assert b"splitting the batch" in r.stderr
+    import hashlib
+    assert hashlib.md5(open(out, "rb").read()).hexdigest() == case["md5_full"]
+
+
+@pytest.mark.parametrize("name", ["zmo", "dmo", "zmo_9"])
+def test_repeat_resets_every_piece_of_step_state(name, emul_exe, tmp_path):
+    """--repeat 2: the second step starts from the state the first one started from (masks, closed pairs incl. their -9 order, coverage, counters), so the files
+    left behind are the golden's; the first step's output is gone and every step adds one line of 33 fields to the --stats file."""
+    case = manifest()["cases"][name]
+    stats = os.path.join(str(tmp_path), "stats.tsv")
+    md5, cont, _ = run_wtzmo_like(emul_exe, case, tmp_path, extra=["--batch", "7", "--repeat", "2", "--stats", stats], exact_pairs=True)
+    assert md5 == case["md5_full"] and cont == case["md5_contained"]
+    assert not os.path.exists(os.path.join(str(tmp_path), "o.ovl.prev"))
+    lines = open(stats).read().split("\n")
+    assert len(lines) == 3 and lines[2] == "" and [len(l.split("\t")) for l in lines[:2]] == [33, 33]
+
+
+@pytest.mark.parametrize("name", ["zmo", "dmo", "zmo_9"])
+@pytest.mark.parametrize("switch", ["WTZ_RANGE_OVERLAP", "WTZ_BATCH_OVERLAP"])
+def test_one_range_or_one_batch_at_a_time(name, switch, emul_exe, tmp_path, monkeypatch):
+    """The strict serial path (ranges planned, computed and committed one after the other) and pipelined ranges without a second batch."""
+    monkeypatch.setenv(switch, "0")
+    case = manifest()["cases"][name]
+    md5, cont, _ = run_wtzmo_like(emul_exe, case, tmp_path, extra=["--batch", "7"], exact_pairs=True)
+    assert md5 == case["md5_full"] and cont == case["md5_contained"]
+
+
+@pytest.mark.parametrize("name", ["zmo_L", "zmo_9"])
+@pytest.mark.parametrize("helpers", ["0", "16"])
+def test_commit_helpers_none_or_many(name, helpers, emul_exe, tmp_path, monkeypatch):
+    """WTZ_COMMIT_HELPERS: no helper thread, and sixteen reading the closed-pair table (zmo_L: preloaded with -L) beside the commit that inserts into it."""
+    monkeypatch.setenv("WTZ_COMMIT_HELPERS", helpers)
+    case = manifest()["cases"][name]
+    md5, cont, _ = run_wtzmo_like(emul_exe, case, tmp_path, extra=["--batch", "7"], exact_pairs=True)
+    assert md5 == case["md5_full"] and cont == case["md5_contained"]
 
 
 @pytest.mark.parametrize("name", ["zmo", "dmo"])

@@ -39,6 +39,17 @@ def test_batch_size_never_changes_the_output(batch, gpu_exe, tmp_path):
     assert md5 == case["md5_full"] and cont == case["md5_contained"]
 
 
+def test_repeat_resets_every_piece_of_step_state(gpu_exe, tmp_path):
+    """--repeat 2 on the device: the second step's files are the golden's, the first step's output is gone, one --stats line of 33 fields per step."""
+    case = manifest()["cases"]["zmo"]
+    stats = os.path.join(str(tmp_path), "stats.tsv")
+    md5, cont, _ = run_wtzmo_like(gpu_exe, case, tmp_path, extra=["--batch", "7", "--repeat", "2", "--stats", stats], exact_pairs=True)
+    assert md5 == case["md5_full"] and cont == case["md5_contained"]
+    assert not os.path.exists(os.path.join(str(tmp_path), "o.ovl.prev"))
+    lines = open(stats).read().split("\n")
+    assert len(lines) == 3 and lines[2] == "" and [len(l.split("\t")) for l in lines[:2]] == [33, 33]
+
+
 @pytest.mark.parametrize("name", ["zmo", "dmo"])
 def test_two_worker_contexts_same_output(name, gpu_exe, tmp_path):
     """--workers 2: wtz_ctx_clone, two HIP streams / scratch pools, batches committed strictly in sequence."""
