@@ -108,6 +108,9 @@ typedef struct {
 	uint64_t n_local, cells_local;                                                    /* its problems and the DP cells (rows x columns of both passes) it executed */
 	double   ms_kext;                                                                 /* K-kext of wtz_kext_batch and of the two extension stages of wtz_align_batch (kernel time, copies excluded) */
 	uint64_t n_kext, cells_kext;                                                      /* its problems and the DP cells (sum of end - beg over the rows executed) */
+	double   ms_kglob;                                                                /* the launch groups of wtz_global_batch and of the last stage of wtz_alignx_batch: K-glob and the wide forms (kernel time, copies excluded) */
+	uint64_t n_kglob, cells_kglob;                                                    /* their problems and DP cells (sum of end - beg over the rows) */
+	uint64_t ticks_kglob_dp, ticks_kglob_tb;                                          /* DIAGNOSTIC ONLY, K-glob only: ticks of the device's constant 100 MHz wall clock (10 ns each), each wavefront's own, summed over the problems: DP rows / traceback with counting.  Only their ratio is meant to be used (the split of ms_kglob, tools/ubench/kglob_bench.py); no caller should depend on the values */
 } wtz_counters_t;
 
 const char *wtz_last_error(void);
@@ -293,9 +296,46 @@ int  wtz_kext_batch(wtz_ctx_t *ctx, const wtz_dp_problem_t *problems, uint32_t n
  * I, D, E, T as kswx_align receives them (costs as negative numbers, e.g. -3, -3, -1, -100): I, D <= 0, E <= -1; 0 <= w <= WTZ_KEXT_MAXW.  W and init_score of
  * the problems are ignored.  out[i]: found, the extended rectangle [tb, te) x [qb, qe) and its score, and the local hit it grew from (local_te / local_qe
  * exclusive too).  The limits of both underlying calls apply (1 <= q_len, t_len <= 65535) and are checked before anything runs: WTZ_E_ARG for the whole call.
- * What kswx_align (kswx.h:1495-1502) does beyond this - one ksw_global2 over the rectangle with its statistics (kswx.h:1443-1482) - is not part of this call. */
+ * What kswx_align (kswx.h:1495-1502) does beyond this - one ksw_global2 over the rectangle with its statistics (kswx.h:1443-1482) - is wtz_alignx_batch below. */
 typedef struct { int32_t found, score, tb, te, qb, qe; int32_t local_score, local_tb, local_te, local_qb, local_qe; } wtz_align_result_t;
 int  wtz_align_batch(wtz_ctx_t *ctx, const wtz_dp_problem_t *problems, uint32_t n, int32_t w, int32_t I, int32_t D, int32_t E, int32_t T, wtz_align_result_t *out);
+
+/* ksw_global2(qlen, query, tlen, target, 4, mat(M, X), o_del, e_del, o_ins, e_ins, w, &n_cigar, &cigar) (ksw.c:503-586) for n independent problems on views of the
+ * uploaded reads: the banded global alignment at ONE band width, W of the problem = w of that call (init_score is ignored).  Rows run over the target, band columns
+ * over the query; the tie rules of ksw.c:549-562 and the walk of ksw.c:571-579 with both of its tails are the reference's.  M and X are the context's params
+ * (1 <= M <= 127, -128 <= X <= 0), the four gap costs are arguments, >= 0 with open + extend <= 32767.
+ * out[i]: score = the return value; aln, mat, mis, ins, del folded from the CIGAR EXACTLY as kswx_gen_cigar_core2 does (kswx.h:1468-1477): op 1 (query only) is
+ * counted in del and op 2 (target only) in ins - the other way round than the fold behind wtz_test_dp; cigar_off / cigar_len of the operations (len << 4 | op, first
+ * operation first) in `cigar` (cigar = NULL with cigar_cap = 0: statistics only, cigar_off = cigar_len = 0); cells = sum of end - beg over the rows;
+ * form_used = the form that ran the problem: 1, 2, 4, 8, 16, 32 = band slots per lane of the K-glob instantiation (up to WTZ_GLOB_MAXSLOTS = 2 047 slots,
+ * slots = min(W, t_len - 1) + min(W, q_len - 1) + 1; the narrowest instantiation that holds them), 33 = the LDS-ring wave DP with its 72 KB slice
+ * (up to 8 190 band columns and 32 k query bases), 255 = the scalar body on one lane (everything else; in the host emulation every wide problem).
+ * LIMITS, all checked before anything is launched (WTZ_E_ARG for the whole call, the context stays usable): 1 <= q_len, t_len <= 65535; W >= 0;
+ * |q_len - t_len| <= W (outside the band the reference returns MINUS_INF and walks back through bytes it never wrote);
+ * 2 * max(o) + max(e) * (q_len + t_len + 2) + max(M, -X) * (max(q_len, t_len) + 1) <= 2^28 (32-bit cells, sentinel at -2^30).
+ * The trace of a launch group comes from the main pool: the library cuts the call into groups that fit it, largest problems first; one problem whose trace does not
+ * fit is WTZ_E_POOL (K-glob: 2 bytes per band slot of the instantiation and row, i.e. 32 * C bytes per row, + 4 * (q_len + t_len) of runs).  The call leaves the
+ * main pool empty. */
+#define WTZ_GLOB_MAXSLOTS 2047
+typedef struct { int32_t score, aln, mat, mis, ins, del; uint32_t cigar_len, form_used; uint64_t cigar_off, cells; } wtz_global_result_t;
+int  wtz_global_batch(wtz_ctx_t *ctx, const wtz_dp_problem_t *problems, uint32_t n, int32_t o_del, int32_t e_del, int32_t o_ins, int32_t e_ins,
+                      wtz_global_result_t *out, uint32_t *cigar, uint64_t cigar_cap);
+
+/* kswx_align / kswx_align_with_cigar(qlen, query, tlen, target, 4, mat(M, X), w, I, D, E, T[, &n_cigar, &cigar]) (kswx.h:1495-1502, 1513-1520) for n independent
+ * problems: the three stages of wtz_align_batch (the same functions), then kswx_gen_cigar_core2 (kswx.h:1443-1482): the band rule of kswx.h:1452-1461 (the
+ * x1 * 1.5 comparison and assignment in double arithmetic truncated to int, w2 from matrix[0] = M and integer division by -E, a negative w = the exact band -w) and
+ * one wtz_global_batch stage over [tb, te) x [qb, qe) with (-D, -E, -I, -E).
+ * out[i]: found; the kswx_t (score = ksw_global2's, the rectangle, aln / mat / mis / ins / del as above); band = the band the rule gave; form_used;
+ * cigar_off / cigar_len as for wtz_global_batch.  found = 0: everything else is 0 (KSWX_NULL).
+ * Arguments and limits as for wtz_align_batch; in addition w in [-1023, -1] is accepted together with T >= 0 (with T < 0 the reference hands the negative band to its
+ * extensions, where lengths go negative: WTZ_E_ARG).  For path scores the rule always yields a band >= |(te - tb) - (qe - qb)|; the library checks that and
+ * fails the call with WTZ_E_STATE instead of running a DP whose corner is outside the band.  With an exact band the caller's input can do that too: a local hit
+ * whose rectangle has |(te - tb) - (qe - qb)| > -w.  That is also WTZ_E_STATE, for the WHOLE call (the text names the problem; no result of the call is valid): the
+ * reference would return MINUS_INF there and walk back through bytes it never wrote, so there is no per-problem result to report.  A caller that cannot rule such hits
+ * out runs wtz_align_batch first and passes only the problems whose rectangle fits its band. */
+typedef struct { int32_t found, score, tb, te, qb, qe, aln, mat, mis, ins, del, band; uint32_t form_used, cigar_len; uint64_t cigar_off; } wtz_alignx_result_t;
+int  wtz_alignx_batch(wtz_ctx_t *ctx, const wtz_dp_problem_t *problems, uint32_t n, int32_t w, int32_t I, int32_t D, int32_t E, int32_t T,
+                      wtz_alignx_result_t *out, uint32_t *cigar, uint64_t cigar_cap);
 
 /* Scratch accounting, so that the caller can size its batches to the pool instead of discovering the limit by WTZ_E_POOL:
  * the context's scratch is cut into a main pool (everything that lives for the batch: match lists, windows, CIGARs) and a transient

@@ -14,6 +14,7 @@
  *   wtz_lib_align.h                wtz_pairs_align: lane pipelines, chained K-sw1, K-sw2, K-sw3 extension jobs, fused stitch
  *   wtz_lib_fetch.h                CIGAR fetch and text rendering
  *   wtz_lib_batch.h                wtz_extend_batch, wtz_local_batch, wtz_kext_batch, wtz_align_batch, the test-only wtz_test_dp
+ *   wtz_lib_glob.h                 wtz_global_batch, wtz_alignx_batch (included by wtz_lib_batch.h)
  *
  * Execution model: every stage is a flat grid of independent tasks (one lane, wavefront or workgroup per read / query / pair /
  * window), 64-thread workgroups so that each wave is scheduled on its own and the thousands of waves per launch spread over all
@@ -32,6 +33,7 @@
 #include "wtz_stitch_fused.h"
 #include "wtz_sw_local.h"
 #include "wtz_sw_kext.h"
+#include "wtz_sw_kglob.h"
 
 /* kernel name tags (rocprofv3 shows wtz_kernel_*<K_pair, ...>) */
 struct K_candidates_wg;
@@ -79,6 +81,9 @@ struct K_zdistinct;
 struct K_zdn;
 struct K_zcount;
 struct K_extcopy;
+struct K_globcopy;
+struct K_glob_ring;
+struct K_glob_scalar;
 
 #include "wtz_dev.h"
 #include "wtz_ctx.h"

@@ -1,6 +1,7 @@
 /*
  * wtz_lib_batch.h — the DP routines as batch services for callers that hold their own problems: wtz_extend_batch (K-sw3), wtz_local_batch (K-local),
- * wtz_kext_batch (K-kext), wtz_align_batch (K-local + K-kext) and, through wtz_testdp.h, the test-only wtz_test_dp.  Included by wtz_lib.cpp.
+ * wtz_kext_batch (K-kext), wtz_align_batch (K-local + K-kext), through wtz_lib_glob.h wtz_global_batch (K-glob) and wtz_alignx_batch (all three) and, through
+ * wtz_testdp.h, the test-only wtz_test_dp.  Included by wtz_lib.cpp.
  */
 /* the two sides of problem i as views of the uploaded reads (h_off: the reads' offsets, fetched by the caller), or WTZ_E_ARG.  allow_empty: a side of
  * length 0 is a problem like any other (its start is not looked at); max_len > 0: the longest side the caller's kernel takes */
@@ -251,16 +252,28 @@ extern "C" int wtz_kext_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32_t
 
 /* kswx_align_no_stat (kswx.h:1504-1511): the local hit of wtz_local_batch, then kswx_extend_core (kswx.h:1386-1441) as two stages of K-kext launches.
  * side 0 = left (the reversed prefixes in front of the hit), 1 = right; role 0 = the problem's target is ksw_extend2's target (rows), 1 = its query is. */
-extern "C" int wtz_align_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32_t n, int32_t w, int32_t I, int32_t D, int32_t E, int32_t T, wtz_align_result_t *out){
+/* the argument checks of wtz_align_batch, under the name of the entry point that makes them */
+static int align_args(const wtz_ctx *c, const char *who, const wtz_dp_problem_t *pr, uint32_t n, const void *out, int32_t w, int32_t I, int32_t D, int32_t E, int32_t T, wtz_kextsc_t *SR){
 	if(!c || !c->bits) return wtz_fail(WTZ_E_ARG, "reads not uploaded");
 	if(n == 0) return WTZ_OK;
 	if(!pr || !out) return wtz_fail(WTZ_E_ARG, "null argument");
-	if(I > 0 || D > 0 || E > -1 || I < -32767 || D < -32767 || E < -32767 || T < -(1 << 30)) return wtz_fail(WTZ_E_ARG, "wtz_align_batch: I and D must be <= 0 and E <= -1 (costs as negative numbers)");
-	if(w < 0 || w > WTZ_KEXT_MAXW) return wtz_fail(WTZ_E_ARG, "wtz_align_batch: band width %d outside [0, %d]", w, WTZ_KEXT_MAXW);
-	wtz_kextsc_t SR[2];      /* by role: kswx.h:1396 / 1422 and, with the opening costs exchanged, kswx.h:1407 / 1431 */
-	CHK(kext_scores(c, "wtz_align_batch", -D, -E, -I, -E, -1, &SR[0]));
-	CHK(kext_scores(c, "wtz_align_batch", -I, -E, -D, -E, -1, &SR[1]));
+	if(I > 0 || D > 0 || E > -1 || I < -32767 || D < -32767 || E < -32767 || T < -(1 << 30)) return wtz_fail(WTZ_E_ARG, "%s: I and D must be <= 0 and E <= -1 (costs as negative numbers)", who);
+	if(w < 0 || w > WTZ_KEXT_MAXW) return wtz_fail(WTZ_E_ARG, "%s: band width %d outside [0, %d]", who, w, WTZ_KEXT_MAXW);
+	/* by role: kswx.h:1396 / 1422 and, with the opening costs exchanged, kswx.h:1407 / 1431 */
+	CHK(kext_scores(c, who, -D, -E, -I, -E, -1, &SR[0]));
+	CHK(kext_scores(c, who, -I, -E, -D, -E, -1, &SR[1]));
+	return WTZ_OK;
+}
+static int align_stages(wtz_ctx *c, const char *entry, const wtz_dp_problem_t *pr, uint32_t n, int32_t w, int32_t I, int32_t D, int32_t E, int32_t T, const wtz_kextsc_t *SR, wtz_align_result_t *out);
+extern "C" int wtz_align_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32_t n, int32_t w, int32_t I, int32_t D, int32_t E, int32_t T, wtz_align_result_t *out){
+	wtz_kextsc_t SR[2];
+	CHK(align_args(c, "wtz_align_batch", pr, n, out, w, I, D, E, T, SR));
+	if(n == 0) return WTZ_OK;
 	CTX_ENTER(c);
+	return align_stages(c, "wtz_align_batch", pr, n, w, I, D, E, T, SR, out);
+}
+/* the three stages of kswx_align_no_stat, shared by wtz_align_batch and wtz_alignx_batch (inside the caller's CTX_ENTER); leaves the main pool empty */
+static int align_stages(wtz_ctx *c, const char *entry, const wtz_dp_problem_t *pr, uint32_t n, int32_t w, int32_t I, int32_t D, int32_t E, int32_t T, const wtz_kextsc_t *SR, wtz_align_result_t *out){
 	/* stage 1; its own checks (1 <= q_len, t_len <= 65535, the views) come before its launch, and nothing else has run by then */
 	std::vector<wtz_local_result_t> loc(n);
 	CHK(wtz_local_batch(c, pr, n, -D, -E, -I, -E, loc.data()));
@@ -315,7 +328,8 @@ extern "C" int wtz_align_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32_
 			}
 		}
 	}
-	return kext_leave(c, "wtz_align_batch");
+	return kext_leave(c, entry);
 }
 
+#include "wtz_lib_glob.h"
 #include "wtz_testdp.h"

@@ -17,7 +17,7 @@ SYMBOLS = [
     "wtz_last_error", "wtz_device_count", "wtz_device_memory", "wtz_ctx_create", "wtz_ctx_destroy", "wtz_ctx_clone", "wtz_upload_reads",
     "wtz_index_build", "wtz_zindex_build", "wtz_candidates", "wtz_candidates_begin", "wtz_candidates_end", "wtz_batch_begin", "wtz_pairs_seed",
     "wtz_pairs_windows", "wtz_pairs_align", "wtz_fetch_cigars", "wtz_fetch_cigar_text", "wtz_fetch_cigar_text_begin", "wtz_fetch_cigar_text_end", "wtz_cigar_text_device", "wtz_host_alloc", "wtz_host_free", "wtz_get_counters", "wtz_reset_counters",
-    "wtz_test_dp", "wtz_extend_batch", "wtz_local_batch", "wtz_kext_batch", "wtz_align_batch", "wtz_pool_info", "wtz_pool_failure_kind",
+    "wtz_test_dp", "wtz_extend_batch", "wtz_local_batch", "wtz_kext_batch", "wtz_align_batch", "wtz_global_batch", "wtz_alignx_batch", "wtz_pool_info", "wtz_pool_failure_kind",
     "wtz_index_count", "wtz_index_counts_fetch", "wtz_index_finish", "wtz_candidate_groups_begin", "wtz_candidate_groups_end", "wtz_candidate_groups_fetch", "wtz_cand_tail_host", "wtz_zindex_build_subset", "wtz_zindex_build_queries", "wtz_upload_reads_ascii", "wtz_fetch_read_bits", "wtz_append_revcomp_views",
 ]
 
@@ -69,6 +69,10 @@ KEXT_RESULT = np.dtype([("score", "<i4"), ("qle", "<i4"), ("tle", "<i4"), ("gtle
 KEXT_MAXW = 1023          # band half-width of one wtz_kext_batch problem (WTZ_KEXT_MAXW)
 KEXT_MAXLEN = 0xFFFFF     # its rows / columns (WTZ_KEXT_MAXLEN)
 ALIGN_RESULT = np.dtype([(n, "<i4") for n in ("found", "score", "tb", "te", "qb", "qe", "local_score", "local_tb", "local_te", "local_qb", "local_qe")])
+GLOBAL_RESULT = np.dtype([(n, "<i4") for n in ("score", "aln", "mat", "mis", "ins", "del")] + [("cigar_len", "<u4"), ("form_used", "<u4"), ("cigar_off", "<u8"), ("cells", "<u8")])
+GLOB_MAXSLOTS = 2047      # band slots of one K-glob wavefront (WTZ_GLOB_MAXSLOTS); wider problems run the wide forms 33 / 255
+ALIGNX_RESULT = np.dtype([(n, "<i4") for n in ("found", "score", "tb", "te", "qb", "qe", "aln", "mat", "mis", "ins", "del", "band")] +
+                         [("form_used", "<u4"), ("cigar_len", "<u4"), ("cigar_off", "<u8")])
 
 
 class Counters(C.Structure):
@@ -78,7 +82,9 @@ class Counters(C.Structure):
                [("ms_ext", C.c_double), ("n_extjobs", C.c_uint64), ("ms_gap", C.c_double), ("bytes_zmer_algo", C.c_uint64),
                 ("ms_ingest", C.c_double), ("bytes_ingest_algo", C.c_uint64),
                 ("ms_local", C.c_double), ("n_local", C.c_uint64), ("cells_local", C.c_uint64),
-                ("ms_kext", C.c_double), ("n_kext", C.c_uint64), ("cells_kext", C.c_uint64)]
+                ("ms_kext", C.c_double), ("n_kext", C.c_uint64), ("cells_kext", C.c_uint64),
+                ("ms_kglob", C.c_double), ("n_kglob", C.c_uint64), ("cells_kglob", C.c_uint64),
+                ("ticks_kglob_dp", C.c_uint64), ("ticks_kglob_tb", C.c_uint64)]
 
 
 def load(path: str | None = None) -> C.CDLL:
@@ -247,6 +253,30 @@ class Context:
         self.lib.wtz_align_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_int32] * 5 + [C.c_void_p]
         self._chk(self.lib.wtz_align_batch(self.h, problems.ctypes.data, problems.size, w, I, D, E, T, out.ctypes.data))
         return out
+
+    def global_batch(self, problems, o_del, e_del, o_ins, e_ins, cigar=True):
+        """ksw_global2 per problem (wtz_global_batch), W = the band: (results, list of CIGAR arrays), or with cigar=False (NULL buffer) the results alone."""
+        problems = np.ascontiguousarray(problems, dtype=DP_PROBLEM)
+        out = np.zeros(problems.size, dtype=GLOBAL_RESULT)
+        cap = int(problems["q_len"].astype(np.int64).sum() + problems["t_len"].astype(np.int64).sum()) + 2 if cigar else 0
+        cig = np.zeros(max(cap, 1), dtype=np.uint32)
+        self.lib.wtz_global_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_uint64]
+        self._chk(self.lib.wtz_global_batch(self.h, problems.ctypes.data, problems.size, o_del, e_del, o_ins, e_ins, out.ctypes.data, cig.ctypes.data if cigar else None, cap))
+        if not cigar:
+            return out
+        return out, [cig[int(o):int(o) + int(n)].copy() for o, n in zip(out["cigar_off"], out["cigar_len"])]
+
+    def alignx_batch(self, problems, w, I, D, E, T, cigar=True):
+        """kswx_align / kswx_align_with_cigar per problem (wtz_alignx_batch); I, D, E, T as negative costs; returns as global_batch does."""
+        problems = np.ascontiguousarray(problems, dtype=DP_PROBLEM)
+        out = np.zeros(problems.size, dtype=ALIGNX_RESULT)
+        cap = int(problems["q_len"].astype(np.int64).sum() + problems["t_len"].astype(np.int64).sum()) + 2 if cigar else 0
+        cig = np.zeros(max(cap, 1), dtype=np.uint32)
+        self.lib.wtz_alignx_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p, C.c_uint64]
+        self._chk(self.lib.wtz_alignx_batch(self.h, problems.ctypes.data, problems.size, w, I, D, E, T, out.ctypes.data, cig.ctypes.data if cigar else None, cap))
+        if not cigar:
+            return out
+        return out, [cig[int(o):int(o) + int(n)].copy() for o, n in zip(out["cigar_off"], out["cigar_len"])]
 
     def counters(self) -> Counters:
         c = Counters()
