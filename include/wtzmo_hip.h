@@ -18,7 +18,9 @@
  *                           with params.refine also kswx_refine_alignment kswx.h:483-659
  *
  *   wtz_local_batch      <- ksw_align2 with KSW_XSTART over ksw_i16         ksw.c:344-366, 233-335 (what kswx_align*, kswx.h:1495-1520, and
- *                           wtcns.c:209, 269 call: the first step of wtcyc, pairaln and wtcns; no tool of this library uses it yet)
+ *                           wtcns.c:209, 269 call: the first step of wtcyc, pairaln and wtcns)
+ *   wtz_alignx_batch     <- kswx_align / kswx_align_with_cigar              kswx.h:1495-1520 (bin/wtcyc, bin/pairaln)
+ *   wtz_pwtext_batch     <- kswx_cigar2pairwise + the marker line           kswx.h:1150-1194, pairaln.c:115-125 (the picture of `pairaln -a`)
  *
  *   wtz_pairs_seed + wtz_pairs_align with params.aux_strand = 1
  *                        <- align_hzmaux, the pair routine of wtgbo   hzm_aln.h:1684-1775 (its caller wtgbo.c:37-56 orients the read first:
@@ -111,6 +113,8 @@ typedef struct {
 	double   ms_kglob;                                                                /* the launch groups of wtz_global_batch and of the last stage of wtz_alignx_batch: K-glob and the wide forms (kernel time, copies excluded) */
 	uint64_t n_kglob, cells_kglob;                                                    /* their problems and DP cells (sum of end - beg over the rows) */
 	uint64_t ticks_kglob_dp, ticks_kglob_tb;                                          /* DIAGNOSTIC ONLY, K-glob only: ticks of the device's constant 100 MHz wall clock (10 ns each), each wavefront's own, summed over the problems: DP rows / traceback with counting.  Only their ratio is meant to be used (the split of ms_kglob, tools/ubench/kglob_bench.py); no caller should depend on the values */
+	double   ms_pwtext;                                                               /* the launch groups of wtz_pwtext_batch: both passes of K-pwtext (kernel time, copies excluded) */
+	uint64_t n_pwtext, bytes_pwtext;                                                  /* its alignments and the bytes of picture written */
 } wtz_counters_t;
 
 const char *wtz_last_error(void);
@@ -336,6 +340,26 @@ int  wtz_global_batch(wtz_ctx_t *ctx, const wtz_dp_problem_t *problems, uint32_t
 typedef struct { int32_t found, score, tb, te, qb, qe, aln, mat, mis, ins, del, band; uint32_t form_used, cigar_len; uint64_t cigar_off; } wtz_alignx_result_t;
 int  wtz_alignx_batch(wtz_ctx_t *ctx, const wtz_dp_problem_t *problems, uint32_t n, int32_t w, int32_t I, int32_t D, int32_t E, int32_t T,
                       wtz_alignx_result_t *out, uint32_t *cigar, uint64_t cigar_cap);
+
+/* kswx_cigar2pairwise(alns, seqs, n_cigar, cigar) (kswx.h:1150-1194) followed by the marker loop of pairaln.c:115-125 for n alignments: the three-line picture
+ * that `pairaln -a` prints.  Alignment i is the view pair problems[i] (q_read / t_read / q_rev / t_rev / q_from / t_from / q_strand / t_strand / q_len / t_len as in
+ * wtz_global_batch; init_score and W are ignored; a side of length 0 is allowed), a start (in[i].qb, in[i].tb) inside the views - seqs[0] = query + qb,
+ * seqs[1] = target + tb, pairaln.c:114 - and the operations cigar[in[i].cigar_off, + in[i].cigar_len), len << 4 | op as wtz_alignx_batch returns them: op 0 writes both
+ * bases, op 1 the query base over '-', op 2 '-' over the target base; operations of length 0 are skipped (kswx.h:1157).  Bases are upper case (bit_base_table).
+ * out[i].cols = the sum of the lengths; the picture is 3 * (cols + 1) bytes at text + out[i].text_off, pictures in input order without gaps: the query line, '\n',
+ * the marker line, '\n', the target line, '\n' (alns[0], alns[2], alns[1]: pairaln.c:126).  Marker: '-' where the query line has '-', else '|' where the lines are
+ * equal, else '-' where the target line has '-', else '*'.  cigar_len = 0 (KSWX_NULL) gives three '\n'.
+ * text = NULL with text_cap = 0 is the sizing call: out[i].cols / text_off only, nothing is launched.
+ * LIMITS, all checked before anything is launched (WTZ_E_ARG for the whole call, the context stays usable): an op other than 0 / 1 / 2 (the reference exits);
+ * a CIGAR that walks past q_len - qb or t_len - tb (the reference reads on); qb / tb outside [0, q_len] / [0, t_len]; a slice outside n_ops; text_cap smaller than
+ * the sum; q_len, t_len <= 65535.
+ * The device picture, the CIGAR words and one 8-byte table entry per operation come from the main pool: the library cuts the call into launch groups that fit it, in
+ * input order (results do not depend on the cut); one alignment that needs more than the main pool (12 bytes per operation + 3 * (cols + 1)) is WTZ_E_POOL.  The
+ * call leaves the main pool empty. */
+typedef struct { int32_t qb, tb; uint32_t cigar_len, pad; uint64_t cigar_off; } wtz_pwtext_in_t;
+typedef struct { uint64_t text_off; uint32_t cols, pad; } wtz_pwtext_result_t;
+int  wtz_pwtext_batch(wtz_ctx_t *ctx, const wtz_dp_problem_t *problems, const wtz_pwtext_in_t *in, uint32_t n, const uint32_t *cigar, uint64_t n_ops,
+                      wtz_pwtext_result_t *out, char *text, uint64_t text_cap);
 
 /* Scratch accounting, so that the caller can size its batches to the pool instead of discovering the limit by WTZ_E_POOL:
  * the context's scratch is cut into a main pool (everything that lives for the batch: match lists, windows, CIGARs) and a transient

@@ -15,6 +15,7 @@
  *   wtz_lib_fetch.h                CIGAR fetch and text rendering
  *   wtz_lib_batch.h                wtz_extend_batch, wtz_local_batch, wtz_kext_batch, wtz_align_batch, the test-only wtz_test_dp
  *   wtz_lib_glob.h                 wtz_global_batch, wtz_alignx_batch (included by wtz_lib_batch.h)
+ *   wtz_lib_pwtext.h               wtz_pwtext_batch (included by wtz_lib_batch.h)
  *
  * Execution model: every stage is a flat grid of independent tasks (one lane, wavefront or workgroup per read / query / pair /
  * window), 64-thread workgroups so that each wave is scheduled on its own and the thousands of waves per launch spread over all
@@ -34,6 +35,7 @@
 #include "wtz_sw_local.h"
 #include "wtz_sw_kext.h"
 #include "wtz_sw_kglob.h"
+#include "wtz_pwtext.h"
 
 /* kernel name tags (rocprofv3 shows wtz_kernel_*<K_pair, ...>) */
 struct K_candidates_wg;

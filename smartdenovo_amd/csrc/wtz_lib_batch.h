@@ -1,6 +1,6 @@
 /*
  * wtz_lib_batch.h — the DP routines as batch services for callers that hold their own problems: wtz_extend_batch (K-sw3), wtz_local_batch (K-local),
- * wtz_kext_batch (K-kext), wtz_align_batch (K-local + K-kext), through wtz_lib_glob.h wtz_global_batch (K-glob) and wtz_alignx_batch (all three) and, through
+ * wtz_kext_batch (K-kext), wtz_align_batch (K-local + K-kext), through wtz_lib_glob.h wtz_global_batch (K-glob) and wtz_alignx_batch (all three) and, through wtz_lib_pwtext.h wtz_pwtext_batch (K-pwtext) and, through
  * wtz_testdp.h, the test-only wtz_test_dp.  Included by wtz_lib.cpp.
  */
 /* the two sides of problem i as views of the uploaded reads (h_off: the reads' offsets, fetched by the caller), or WTZ_E_ARG.  allow_empty: a side of
@@ -332,4 +332,5 @@ static int align_stages(wtz_ctx *c, const char *entry, const wtz_dp_problem_t *p
 }
 
 #include "wtz_lib_glob.h"
+#include "wtz_lib_pwtext.h"
 #include "wtz_testdp.h"

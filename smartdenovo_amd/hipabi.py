@@ -17,7 +17,7 @@ SYMBOLS = [
     "wtz_last_error", "wtz_device_count", "wtz_device_memory", "wtz_ctx_create", "wtz_ctx_destroy", "wtz_ctx_clone", "wtz_upload_reads",
     "wtz_index_build", "wtz_zindex_build", "wtz_candidates", "wtz_candidates_begin", "wtz_candidates_end", "wtz_batch_begin", "wtz_pairs_seed",
     "wtz_pairs_windows", "wtz_pairs_align", "wtz_fetch_cigars", "wtz_fetch_cigar_text", "wtz_fetch_cigar_text_begin", "wtz_fetch_cigar_text_end", "wtz_cigar_text_device", "wtz_host_alloc", "wtz_host_free", "wtz_get_counters", "wtz_reset_counters",
-    "wtz_test_dp", "wtz_extend_batch", "wtz_local_batch", "wtz_kext_batch", "wtz_align_batch", "wtz_global_batch", "wtz_alignx_batch", "wtz_pool_info", "wtz_pool_failure_kind",
+    "wtz_test_dp", "wtz_extend_batch", "wtz_local_batch", "wtz_kext_batch", "wtz_align_batch", "wtz_global_batch", "wtz_alignx_batch", "wtz_pwtext_batch", "wtz_pool_info", "wtz_pool_failure_kind",
     "wtz_index_count", "wtz_index_counts_fetch", "wtz_index_finish", "wtz_candidate_groups_begin", "wtz_candidate_groups_end", "wtz_candidate_groups_fetch", "wtz_cand_tail_host", "wtz_zindex_build_subset", "wtz_zindex_build_queries", "wtz_upload_reads_ascii", "wtz_fetch_read_bits", "wtz_append_revcomp_views",
 ]
 
@@ -73,6 +73,8 @@ GLOBAL_RESULT = np.dtype([(n, "<i4") for n in ("score", "aln", "mat", "mis", "in
 GLOB_MAXSLOTS = 2047      # band slots of one K-glob wavefront (WTZ_GLOB_MAXSLOTS); wider problems run the wide forms 33 / 255
 ALIGNX_RESULT = np.dtype([(n, "<i4") for n in ("found", "score", "tb", "te", "qb", "qe", "aln", "mat", "mis", "ins", "del", "band")] +
                          [("form_used", "<u4"), ("cigar_len", "<u4"), ("cigar_off", "<u8")])
+PWTEXT_IN = np.dtype([("qb", "<i4"), ("tb", "<i4"), ("cigar_len", "<u4"), ("pad", "<u4"), ("cigar_off", "<u8")])
+PWTEXT_RESULT = np.dtype([("text_off", "<u8"), ("cols", "<u4"), ("pad", "<u4")])
 
 
 class Counters(C.Structure):
@@ -84,7 +86,8 @@ class Counters(C.Structure):
                 ("ms_local", C.c_double), ("n_local", C.c_uint64), ("cells_local", C.c_uint64),
                 ("ms_kext", C.c_double), ("n_kext", C.c_uint64), ("cells_kext", C.c_uint64),
                 ("ms_kglob", C.c_double), ("n_kglob", C.c_uint64), ("cells_kglob", C.c_uint64),
-                ("ticks_kglob_dp", C.c_uint64), ("ticks_kglob_tb", C.c_uint64)]
+                ("ticks_kglob_dp", C.c_uint64), ("ticks_kglob_tb", C.c_uint64),
+                ("ms_pwtext", C.c_double), ("n_pwtext", C.c_uint64), ("bytes_pwtext", C.c_uint64)]
 
 
 def load(path: str | None = None) -> C.CDLL:
@@ -277,6 +280,27 @@ class Context:
         if not cigar:
             return out
         return out, [cig[int(o):int(o) + int(n)].copy() for o, n in zip(out["cigar_off"], out["cigar_len"])]
+
+    def pwtext_batch(self, problems, starts, cigar_slices, cigar, sizing_only=False):
+        """the picture of `pairaln -a` per alignment (wtz_pwtext_batch): starts = (qb, tb) pairs, cigar_slices = (offset, length) pairs into `cigar`;
+        returns (results, bytes), the picture of alignment i at bytes[text_off : text_off + 3 * (cols + 1)]; sizing_only: the NULL-buffer call, (results, b"")"""
+        problems = np.ascontiguousarray(problems, dtype=DP_PROBLEM)
+        cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
+        inp = np.zeros(problems.size, dtype=PWTEXT_IN)
+        if problems.size:
+            st = np.asarray(starts, dtype=np.int64).reshape(-1, 2)
+            sl = np.asarray(cigar_slices, dtype=np.uint64).reshape(-1, 2)
+            inp["qb"], inp["tb"], inp["cigar_off"], inp["cigar_len"] = st[:, 0], st[:, 1], sl[:, 0], sl[:, 1]
+        out = np.zeros(problems.size, dtype=PWTEXT_RESULT)
+        self.lib.wtz_pwtext_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]
+        args = (self.h, problems.ctypes.data, inp.ctypes.data, problems.size, cigar.ctypes.data if cigar.size else None, cigar.size, out.ctypes.data)
+        self._chk(self.lib.wtz_pwtext_batch(*args, None, 0))
+        if sizing_only or problems.size == 0:
+            return out, b""
+        cap = int(out["text_off"][-1]) + 3 * (int(out["cols"][-1]) + 1)
+        buf = np.zeros(cap, dtype=np.uint8)
+        self._chk(self.lib.wtz_pwtext_batch(*args, buf.ctypes.data, cap))
+        return out, buf.tobytes()
 
     def counters(self) -> Counters:
         c = Counters()
