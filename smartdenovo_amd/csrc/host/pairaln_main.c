@@ -20,12 +20,9 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <unistd.h>
-#include <getopt.h>
 #include "wtzmo_hip.h"
-#include "wtz_host.h"
+#include "wtz_tool.h"
 
-#define PA_MAXLEN 65535
 #define PA_MAXW 1023
 
 static int usage(void){
@@ -57,20 +54,41 @@ static int usage(void){
 
 typedef struct {
 	wtz_ctx_t *ctx; int W, O, E, T, bidir, has_aln;
-	hx_store_t st;                                   /* the block: names, lengths, the bases as text; records 2k and 2k + 1 are pair k */
-	uint64_t *rdoff; uint32_t *rdlen; size_t cap_rd;
+	hx_store_t st; ht_block_t blk;                   /* the block: names, lengths, the bases as text; records 2k and 2k + 1 are pair k */
 	wtz_dp_problem_t *pr; wtz_alignx_result_t *rs; wtz_pwtext_in_t *in; wtz_pwtext_result_t *tx, *tx2; uint32_t *slot; size_t cap_pr;
 	uint32_t *cigar; uint64_t cap_cigar; char *text; uint64_t cap_text;
+	uint32_t m; uint64_t cig_at, need_text;          /* of the block in hand: its problems, its CIGAR words so far, the bytes of its pictures */
 } pa_t;
 
-static void pa_die(const char *what){ fprintf(stderr, " -- %s failed: %s --\n", what, wtz_last_error()); exit(1); }
+/* problems [at, at + step): their CIGARs go behind those of the problems before */
+static int pa_align(void *user, uint32_t at, uint32_t step){
+	pa_t *C = (pa_t*)user;
+	const int rc = wtz_alignx_batch(C->ctx, C->pr + at, step, C->W, C->O, C->O, C->E, C->T, C->rs + at, C->cigar + C->cig_at, C->cap_cigar - C->cig_at);
+	if(rc == WTZ_E_STATE){      /* which pair: its problem alone */
+		for(uint32_t i = at; i < at + step; i++) if(wtz_alignx_batch(C->ctx, C->pr + i, 1, C->W, C->O, C->O, C->E, C->T, C->rs + i, NULL, 0) == WTZ_E_STATE){
+			fprintf(stderr, " -- records '%s' and '%s' (%c strand): the extended hit lies outside the band of its global alignment, where the reference reads memory it never wrote: %s --\n",
+				C->st.reads[C->pr[i].q_read].name, C->st.reads[C->pr[i].t_read].name, "+-"[C->pr[i].t_rev], wtz_last_error());
+			HT_EXIT();
+		}
+	}
+	if(rc != WTZ_OK) return rc;
+	uint64_t used = 0;
+	for(uint32_t i = at; i < at + step; i++){ C->rs[i].cigar_off += C->cig_at; used += C->rs[i].cigar_len; }
+	C->cig_at += used;
+	return WTZ_OK;
+}
+/* the offsets of the sizing call stay: pictures lie one behind the other, a part of the block renders into its own stretch of the buffer */
+static int pa_render(void *user, uint32_t at, uint32_t step){
+	pa_t *C = (pa_t*)user;
+	const uint64_t t0 = C->tx[at].text_off, t1 = at + step < C->m ? C->tx[at + step].text_off : C->need_text;
+	return wtz_pwtext_batch(C->ctx, C->pr + at, C->in + at, step, C->cigar, C->cig_at, C->tx2 + at, C->text + t0, t1 - t0);
+}
 
 /* one block: upload, wtz_alignx_batch over the problems of its pairs without an empty record (halved on WTZ_E_POOL), wtz_pwtext_batch over the same problems, the lines */
 static void pa_block(pa_t *C){
 	hx_store_t *st = &C->st;
 	const uint32_t n = st->n_all, npair = n / 2, nd = C->bidir == 3 ? 2 : 1;
 	if(n == 0) return;
-	if(n > C->cap_rd){ C->cap_rd = n; C->rdoff = (uint64_t*)hx_realloc(C->rdoff, 8 * (size_t)n); C->rdlen = (uint32_t*)hx_realloc(C->rdlen, 4 * (size_t)n); }
 	if((size_t)npair * nd > C->cap_pr){
 		C->cap_pr = (size_t)npair * nd;
 		C->pr = (wtz_dp_problem_t*)hx_realloc(C->pr, sizeof(wtz_dp_problem_t) * C->cap_pr); C->rs = (wtz_alignx_result_t*)hx_realloc(C->rs, sizeof(wtz_alignx_result_t) * C->cap_pr);
@@ -78,7 +96,6 @@ static void pa_block(pa_t *C){
 		C->slot = (uint32_t*)hx_realloc(C->slot, 4 * C->cap_pr);
 	}
 	uint32_t m = 0; uint64_t need_cigar = 2;
-	for(uint32_t i = 0; i < n; i++){ C->rdoff[i] = st->reads[i].off; C->rdlen[i] = st->reads[i].len; }
 	for(uint32_t k = 0; k < npair; k++) for(uint32_t d = 0; d < nd; d++){
 		C->slot[k * nd + d] = UINT32_MAX;
 		if(st->reads[2 * k].len == 0 || st->reads[2 * k + 1].len == 0) continue;      /* an empty record: no hit, nothing for the device */
@@ -90,47 +107,18 @@ static void pa_block(pa_t *C){
 	}
 	if(m){
 		if(need_cigar > C->cap_cigar){ C->cap_cigar = need_cigar; C->cigar = (uint32_t*)hx_realloc(C->cigar, 4 * (size_t)need_cigar); }
-		if(wtz_upload_reads_ascii(C->ctx, st->text, st->nbase, C->rdoff, C->rdlen, n, 0, NULL) != WTZ_OK) pa_die("wtz_upload_reads_ascii");
-		uint64_t cig_at = 0;
-		for(uint32_t at = 0, step = m; at < m; ){
-			if(step > m - at) step = m - at;
-			const int rc = wtz_alignx_batch(C->ctx, C->pr + at, step, C->W, C->O, C->O, C->E, C->T, C->rs + at, C->cigar + cig_at, C->cap_cigar - cig_at);
-			if(rc == WTZ_E_POOL){
-				if(step == 1){ fprintf(stderr, " -- scratch pool too small even for one pair: %s (use --pool-gb) --\n", wtz_last_error()); exit(1); }
-				step = (step + 1) / 2; continue;
-			}
-			if(rc == WTZ_E_STATE){      /* which pair: its problem alone */
-				for(uint32_t i = at; i < at + step; i++) if(wtz_alignx_batch(C->ctx, C->pr + i, 1, C->W, C->O, C->O, C->E, C->T, C->rs + i, NULL, 0) == WTZ_E_STATE){
-					fprintf(stderr, " -- records '%s' and '%s' (%c strand): the extended hit lies outside the band of its global alignment, where the reference reads memory it never wrote: %s --\n",
-						st->reads[C->pr[i].q_read].name, st->reads[C->pr[i].t_read].name, "+-"[C->pr[i].t_rev], wtz_last_error());
-					exit(1);
-				}
-			}
-			if(rc != WTZ_OK) pa_die("wtz_alignx_batch");
-			uint64_t used = 0;
-			for(uint32_t i = at; i < at + step; i++){ C->rs[i].cigar_off += cig_at; used += C->rs[i].cigar_len; }
-			cig_at += used; at += step;
-		}
+		ht_block_upload(C->ctx, &C->blk, st);
+		C->m = m; C->cig_at = 0;
+		ht_halving(m, pa_align, C, "wtz_alignx_batch", "pair", 1);
 		if(C->has_aln){
 			for(uint32_t i = 0; i < m; i++){
 				wtz_pwtext_in_t *x = &C->in[i]; memset(x, 0, sizeof *x);
 				x->qb = C->rs[i].qb; x->tb = C->rs[i].tb; x->cigar_off = C->rs[i].cigar_off; x->cigar_len = C->rs[i].cigar_len;
 			}
-			if(wtz_pwtext_batch(C->ctx, C->pr, C->in, m, C->cigar, cig_at, C->tx, NULL, 0) != WTZ_OK) pa_die("wtz_pwtext_batch");
-			const uint64_t need_text = C->tx[m - 1].text_off + 3ull * ((uint64_t)C->tx[m - 1].cols + 1);
-			if(need_text > C->cap_text){ C->cap_text = need_text; C->text = (char*)hx_realloc(C->text, (size_t)need_text); }
-			/* the offsets of the sizing call stay: pictures lie one behind the other, a part of the block renders into its own stretch of the buffer */
-			for(uint32_t at = 0, step = m; at < m; ){
-				if(step > m - at) step = m - at;
-				const uint64_t t0 = C->tx[at].text_off, t1 = at + step < m ? C->tx[at + step].text_off : need_text;
-				const int rc = wtz_pwtext_batch(C->ctx, C->pr + at, C->in + at, step, C->cigar, cig_at, C->tx2 + at, C->text + t0, t1 - t0);
-				if(rc == WTZ_E_POOL){
-					if(step == 1){ fprintf(stderr, " -- scratch pool too small even for one picture: %s (use --pool-gb) --\n", wtz_last_error()); exit(1); }
-					step = (step + 1) / 2; continue;
-				}
-				if(rc != WTZ_OK) pa_die("wtz_pwtext_batch");
-				at += step;
-			}
+			if(wtz_pwtext_batch(C->ctx, C->pr, C->in, m, C->cigar, C->cig_at, C->tx, NULL, 0) != WTZ_OK) ht_die("wtz_pwtext_batch");
+			C->need_text = C->tx[m - 1].text_off + 3ull * ((uint64_t)C->tx[m - 1].cols + 1);
+			if(C->need_text > C->cap_text){ C->cap_text = C->need_text; C->text = (char*)hx_realloc(C->text, (size_t)C->need_text); }
+			ht_halving(m, pa_render, C, "wtz_pwtext_batch", "picture", 1);
 		}
 	}
 	for(uint32_t k = 0; k < npair; k++){
@@ -149,14 +137,13 @@ static void pa_block(pa_t *C){
 			}
 		}
 	}
-	for(uint32_t i = 0; i < n; i++) free(st->reads[i].name);
-	st->n_all = 0; st->nbase = 0;
+	ht_block_done(st);
 }
 
 int main(int argc, char **argv){
-	int c, W = 800, M = 2, X = -5, O = -3, E = -1, T = -100, bidir = 1, has_aln = 0, gpu = 0;
-	uint64_t pool_gb = 0, block_bytes = (uint64_t)64 << 20;
-	static const struct option longopts[] = { {"gpu", required_argument, NULL, 1001}, {"pool-gb", required_argument, NULL, 1002}, {"block-bytes", required_argument, NULL, 1003}, {NULL, 0, NULL, 0} };
+	int c, W = 800, M = 2, X = -5, O = -3, E = -1, T = -100, bidir = 1, has_aln = 0;
+	ht_devopt_t dev = { 0, 0, 0, (uint64_t)64 << 20 };
+	static const struct option longopts[] = { HT_LONGOPTS("block-bytes"), {NULL, 0, NULL, 0} };
 	while((c = getopt_long(argc, argv, "hsW:M:X:O:E:T:a", longopts, NULL)) != -1){
 		switch(c){
 			case 'h': return usage();
@@ -168,22 +155,16 @@ int main(int argc, char **argv){
 			case 'O': O = atoi(optarg); break;
 			case 'E': E = atoi(optarg); break;
 			case 'T': T = atoi(optarg); break;
-			case 1001: gpu = atoi(optarg); break;
-			case 1002: pool_gb = (uint64_t)atoll(optarg); break;
-			case 1003: block_bytes = (uint64_t)atoll(optarg); break;
-			default: return usage();
+			default: if(!ht_devopt(&dev, c, optarg)) return usage();
 		}
 	}
 	if(W > PA_MAXW || W < -PA_MAXW){ fprintf(stderr, " -- -W %d: this build aligns with a bandwidth of at most %d --\n", W, PA_MAXW); return 1; }
 	if(W < 0 && T < 0){ fprintf(stderr, " -- -W %d with -T %d: a negative bandwidth (the exact band) needs -T 0 or above --\n", W, T); return 1; }
-	if(wtz_device_count() <= 0){ fprintf(stderr, " -- no HIP device visible: pairaln (MI355X build) has no CPU path for the alignment: %s --\n", wtz_last_error()); return 1; }
-	wtz_params_c P; memset(&P, 0, sizeof P);
-	P.ksize = 16; P.zsize = 10; P.hk = 1; P.hz = 1; P.ksave = 4; P.kovl = 300; P.ncand = 500; P.nbest = 100; P.kwin = 800; P.kstep = 400; P.ztot = 300; P.zovl = 200;
-	P.max_zmer_freq = 64; P.max_kmer_var = 2; P.win_rep_norm = 20; P.win_rep_cutoff = 100;
-	P.w = 50; P.ew = 800; P.W = 3200; P.M = M; P.X = X; P.O = O; P.E = E; P.T = T; P.min_score = 200; P.min_id = 0.5f;
-	P.xvar = 128; P.yvar = 64; P.min_block_len = 160; P.max_overhang = 256; P.deviation_penalty = 1.0f; P.gap_penalty = 0.05f;
+	if(ht_no_device("pairaln", "alignment")) return 1;
+	wtz_params_c P; ht_default_params(&P);
+	P.M = M; P.X = X; P.O = O; P.E = E; P.T = T;
 	pa_t C; memset(&C, 0, sizeof C);
-	if(wtz_ctx_create(gpu, &P, (pool_gb ? pool_gb : 16) << 30, &C.ctx) != WTZ_OK) pa_die("wtz_ctx_create");
+	C.ctx = ht_ctx_create(&dev, &P);
 	C.W = W; C.O = O; C.E = E; C.T = T; C.bidir = bidir; C.has_aln = has_aln; C.st.keep_text = 1;
 	char *dash[1] = { (char*)"-" };
 	hx_reader_t *fr = optind < argc ? hx_reader_open(argv + optind, argc - optind) : hx_reader_open(dash, 1);
@@ -193,12 +174,10 @@ int main(int argc, char **argv){
 		if(!hx_reader_seq(fr, &name[0], &seq[0]) || !hx_reader_seq(fr, &name[1], &seq[1])) break;      /* pairaln.c:94: a trailing unpaired record is dropped */
 		uint64_t add = 0;
 		for(int k = 0; k < 2; k++){
-			if(seq[k].n > PA_MAXLEN){ fprintf(stderr, " -- record '%.*s' has %llu bases: more than %d, the longest record this build aligns --\n", (int)name[k].n, name[k].s, (unsigned long long)seq[k].n, PA_MAXLEN); return 1; }
-			for(size_t i = 0; i < seq[k].n; i++) if(strchr("ACGTacgt", seq[k].s[i]) == NULL || seq[k].s[i] == 0){
-				fprintf(stderr, " -- record '%.*s' has a character outside ACGTacgt at base %llu (0x%02x) --\n", (int)name[k].n, name[k].s, (unsigned long long)i, (unsigned)(unsigned char)seq[k].s[i]); return 1; }
+			ht_check_record("record", &name[k], &seq[k]);
 			add += seq[k].n;
 		}
-		if(C.st.n_all && C.st.nbase + add > block_bytes) pa_block(&C);
+		if(C.st.n_all && C.st.nbase + add > dev.block) pa_block(&C);
 		for(int k = 0; k < 2; k++) hx_store_add(&C.st, name[k].s, name[k].n, seq[k].s, seq[k].n);
 	}
 	pa_block(&C);

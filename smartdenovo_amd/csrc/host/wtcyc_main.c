@@ -16,12 +16,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <unistd.h>
-#include <getopt.h>
 #include "wtzmo_hip.h"
-#include "wtz_host.h"
-
-#define WC_MAXLEN 65535
+#include "wtz_tool.h"
 
 typedef struct { int32_t score, tb, te, qb, qe, aln, mat, mis, ins, del; } wc_kswx_t;      /* kswx_t */
 
@@ -77,11 +73,14 @@ static void output_alignment(const char *name, int seqlen, wc_kswx_t x, int ms, 
 
 typedef struct {
 	wtz_ctx_t *ctx; int W, O, E, T, ms; float mi; FILE *alno, *cbto;
-	hx_store_t st;                                   /* the block: names, lengths, the bases as text */
-	uint64_t *rdoff; uint32_t *rdlen; wtz_dp_problem_t *pr; wtz_alignx_result_t *rs; uint32_t *slot; size_t cap;
+	hx_store_t st; ht_block_t blk;                   /* the block: names, lengths, the bases as text */
+	wtz_dp_problem_t *pr; wtz_alignx_result_t *rs; uint32_t *slot; size_t cap;
 } wc_t;
 
-static void wc_die(const char *what){ fprintf(stderr, " -- %s failed: %s --\n", what, wtz_last_error()); exit(1); }
+static int wc_align(void *user, uint32_t at, uint32_t step){
+	wc_t *C = (wc_t*)user;
+	return wtz_alignx_batch(C->ctx, C->pr + at, step, C->W, C->O, C->O, C->E, C->T, C->rs + at, NULL, 0);
+}
 
 /* one block: upload, one wtz_alignx_batch over its non-empty reads (halved on WTZ_E_POOL), the lines in read order */
 static void wc_block(wc_t *C){
@@ -89,30 +88,20 @@ static void wc_block(wc_t *C){
 	const uint32_t n = st->n_all;
 	if(n == 0) return;
 	if(n > C->cap){
-		C->cap = n;
-		C->rdoff = (uint64_t*)hx_realloc(C->rdoff, 8 * (size_t)n); C->rdlen = (uint32_t*)hx_realloc(C->rdlen, 4 * (size_t)n); C->slot = (uint32_t*)hx_realloc(C->slot, 4 * (size_t)n);
+		C->cap = n; C->slot = (uint32_t*)hx_realloc(C->slot, 4 * (size_t)n);
 		C->pr = (wtz_dp_problem_t*)hx_realloc(C->pr, sizeof(wtz_dp_problem_t) * n); C->rs = (wtz_alignx_result_t*)hx_realloc(C->rs, sizeof(wtz_alignx_result_t) * n);
 	}
 	uint32_t m = 0;
 	for(uint32_t i = 0; i < n; i++){
-		C->rdoff[i] = st->reads[i].off; C->rdlen[i] = st->reads[i].len; C->slot[i] = UINT32_MAX;
+		C->slot[i] = UINT32_MAX;
 		if(st->reads[i].len == 0) continue;          /* an empty record: no hit, nothing for the device */
 		wtz_dp_problem_t *p = &C->pr[m]; memset(p, 0, sizeof *p);
 		p->q_read = p->t_read = i; p->q_rev = 1; p->t_rev = 0; p->q_strand = p->t_strand = 1; p->q_len = p->t_len = (int32_t)st->reads[i].len;
 		C->slot[i] = m++;
 	}
 	if(m){
-		if(wtz_upload_reads_ascii(C->ctx, st->text, st->nbase, C->rdoff, C->rdlen, n, 0, NULL) != WTZ_OK) wc_die("wtz_upload_reads_ascii");
-		for(uint32_t at = 0, step = m; at < m; ){
-			if(step > m - at) step = m - at;
-			const int rc = wtz_alignx_batch(C->ctx, C->pr + at, step, C->W, C->O, C->O, C->E, C->T, C->rs + at, NULL, 0);
-			if(rc == WTZ_E_POOL){
-				if(step == 1){ fprintf(stderr, " -- scratch pool too small even for one read: %s (use --pool-gb) --\n", wtz_last_error()); exit(1); }
-				step = (step + 1) / 2; continue;
-			}
-			if(rc != WTZ_OK) wc_die("wtz_alignx_batch");
-			at += step;
-		}
+		ht_block_upload(C->ctx, &C->blk, st);
+		ht_halving(m, wc_align, C, "wtz_alignx_batch", "read", 1);
 	}
 	for(uint32_t i = 0; i < n; i++){
 		wc_kswx_t x; memset(&x, 0, sizeof x);            /* KSWX_NULL */
@@ -121,17 +110,16 @@ static void wc_block(wc_t *C){
 			x.score = r->score; x.tb = r->tb; x.te = r->te; x.qb = r->qb; x.qe = r->qe; x.aln = r->aln; x.mat = r->mat; x.mis = r->mis; x.ins = r->ins; x.del = r->del;
 		}
 		if(x.score >= 0) output_alignment(st->reads[i].name, (int)st->reads[i].len, x, C->ms, C->mi, C->alno, C->cbto);      /* wtcyc.c:169 */
-		free(st->reads[i].name);
 	}
-	st->n_all = 0; st->nbase = 0;
+	ht_block_done(st);
 }
 
 int main(int argc, char **argv){
 	char *alnf = NULL, *cbtf = NULL;
-	int c, n_job = 1, i_job = 0, W = 800, M = 2, X = -5, O = -3, E = -1, T = -100, ms = 400, overwrite = 0, gpu = 0;
-	uint64_t pool_gb = 0, block_bytes = (uint64_t)256 << 20;
+	int c, n_job = 1, i_job = 0, W = 800, M = 2, X = -5, O = -3, E = -1, T = -100, ms = 400, overwrite = 0;
+	ht_devopt_t dev = { 0, 0, 0, (uint64_t)256 << 20 };
 	float mi = 0.7;
-	static const struct option longopts[] = { {"gpu", required_argument, NULL, 1001}, {"pool-gb", required_argument, NULL, 1002}, {"block-bytes", required_argument, NULL, 1003}, {NULL, 0, NULL, 0} };
+	static const struct option longopts[] = { HT_LONGOPTS("block-bytes"), {NULL, 0, NULL, 0} };
 	while((c = getopt_long(argc, argv, "ht:P:p:o:a:fs:m:M:X:O:E:W:T:", longopts, NULL)) != -1){
 		switch(c){
 			case 'h': return usage();
@@ -149,10 +137,7 @@ int main(int argc, char **argv){
 			case 'E': E = atoi(optarg); break;
 			case 'W': W = atoi(optarg); break;
 			case 'T': T = atoi(optarg); break;
-			case 1001: gpu = atoi(optarg); break;
-			case 1002: pool_gb = (uint64_t)atoll(optarg); break;
-			case 1003: block_bytes = (uint64_t)atoll(optarg); break;
-			default: return usage();
+			default: if(!ht_devopt(&dev, c, optarg)) return usage();
 		}
 	}
 	if(optind == argc) return usage();
@@ -166,14 +151,11 @@ int main(int argc, char **argv){
 		fprintf(stderr, "File exists! '%s'\n\n", cbtf);
 		return usage();
 	}
-	if(wtz_device_count() <= 0){ fprintf(stderr, " -- no HIP device visible: wtcyc (MI355X build) has no CPU path for the alignment: %s --\n", wtz_last_error()); return 1; }
-	wtz_params_c P; memset(&P, 0, sizeof P);
-	P.ksize = 16; P.zsize = 10; P.hk = 1; P.hz = 1; P.ksave = 4; P.kovl = 300; P.ncand = 500; P.nbest = 100; P.kwin = 800; P.kstep = 400; P.ztot = 300; P.zovl = 200;
-	P.max_zmer_freq = 64; P.max_kmer_var = 2; P.win_rep_norm = 20; P.win_rep_cutoff = 100;
-	P.w = 50; P.ew = 800; P.W = 3200; P.M = M; P.X = X; P.O = O; P.E = E; P.T = T; P.min_score = 200; P.min_id = 0.5f;
-	P.xvar = 128; P.yvar = 64; P.min_block_len = 160; P.max_overhang = 256; P.deviation_penalty = 1.0f; P.gap_penalty = 0.05f;
+	if(ht_no_device("wtcyc", "alignment")) return 1;
+	wtz_params_c P; ht_default_params(&P);
+	P.M = M; P.X = X; P.O = O; P.E = E; P.T = T;
 	wc_t C; memset(&C, 0, sizeof C);
-	if(wtz_ctx_create(gpu, &P, (pool_gb ? pool_gb : 16) << 30, &C.ctx) != WTZ_OK) wc_die("wtz_ctx_create");
+	C.ctx = ht_ctx_create(&dev, &P);
 	C.W = W; C.O = O; C.E = E; C.T = T; C.ms = ms; C.mi = mi; C.st.keep_text = 1;
 	C.alno = alnf ? ((strcmp(alnf, "-") == 0) ? stdout : fopen(alnf, "w")) : NULL;
 	C.cbto = cbtf ? ((strcmp(cbtf, "-") == 0) ? stdout : fopen(cbtf, "w")) : stdout;
@@ -184,10 +166,8 @@ int main(int argc, char **argv){
 	uint64_t n_rd = 0;
 	while(hx_reader_seq(fr, &name, &seq)){
 		if(((int)(n_rd ++) % n_job) != i_job) continue;
-		if(seq.n > WC_MAXLEN){ fprintf(stderr, " -- read '%.*s' has %llu bases: more than %d, the longest read this build aligns --\n", (int)name.n, name.s, (unsigned long long)seq.n, WC_MAXLEN); return 1; }
-		for(size_t i = 0; i < seq.n; i++) if(strchr("ACGTacgt", seq.s[i]) == NULL || seq.s[i] == 0){
-			fprintf(stderr, " -- read '%.*s' has a character outside ACGTacgt at base %llu (0x%02x) --\n", (int)name.n, name.s, (unsigned long long)i, (unsigned)(unsigned char)seq.s[i]); return 1; }
-		if(C.st.n_all && C.st.nbase + seq.n > block_bytes) wc_block(&C);
+		ht_check_record("read", &name, &seq);
+		if(C.st.n_all && C.st.nbase + seq.n > dev.block) wc_block(&C);
 		hx_store_add(&C.st, name.s, name.n, seq.s, seq.n);
 	}
 	wc_block(&C);

@@ -19,13 +19,10 @@
 #ifndef WTEXT_CORE_H
 #define WTEXT_CORE_H
 
-#include <getopt.h>
-#include <pthread.h>
 #include <time.h>
-#include <unistd.h>
-#include "wtz_host.h"
-
 #define WX_DIE() do { fflush(NULL); _exit(1); } while(0)      /* the device context may be under construction on a helper thread: never exit() under it */
+#define HT_EXIT() WX_DIE()
+#include "wtz_tool.h"
 
 typedef struct { char **a; int n, cap; } wx_strlist_t;
 static void wx_sl_push(wx_strlist_t *l, char *s){ if(l->n == l->cap){ l->cap = l->cap ? l->cap * 2 : 4; l->a = (char**)hx_realloc(l->a, sizeof(char*) * (size_t)l->cap); } l->a[l->n++] = s; }
@@ -33,7 +30,7 @@ static void wx_sl_push(wx_strlist_t *l, char *s){ if(l->n == l->cap){ l->cap = l
 typedef struct {
 	int ncpu, n_job, i_job, W, M, X, O, E, T, max_ext, overwrite;
 	wx_strlist_t pbs, ovls, obts, cycs; char *output;
-	int gpu; uint64_t pool_gb; uint32_t block;      /* ours: device, scratch, overlaps per device block */
+	ht_devopt_t dev; uint32_t block;      /* ours: device and scratch, overlaps per device block */
 } wx_opt_t;
 
 typedef struct { int32_t score, tb, te, qb, qe, aln, mat, mis, ins, del; } wx_aln_t;      /* kswx_t */
@@ -90,7 +87,7 @@ static int wx_parse_args(wx_opt_t *o, int argc, char **argv){
 	memset(o, 0, sizeof *o);
 	o->ncpu = 1; o->n_job = 1; o->i_job = 0; o->W = 800; o->M = 2; o->X = -5; o->O = -3; o->E = -1; o->T = -100; o->max_ext = 400;      /* wtext.c:397-404 */
 	o->block = 65536;
-	static const struct option lopts[] = { {"gpu", 1, 0, 1001}, {"pool-gb", 1, 0, 1002}, {"block", 1, 0, 1003}, {0, 0, 0, 0} };
+	static const struct option lopts[] = { HT_LONGOPTS("block"), {0, 0, 0, 0} };
 	int c; optind = 1;
 	while((c = getopt_long(argc, argv, "hft:P:p:i:B:b:j:o:W:M:X:O:E:T:s:m:", lopts, NULL)) != -1){      /* wtext.c:406: no 'S' */
 		switch(c){
@@ -111,10 +108,7 @@ static int wx_parse_args(wx_opt_t *o, int argc, char **argv){
 			case 'E': o->E = atoi(optarg); break;
 			case 'T': o->T = atoi(optarg); break;
 			case 's': case 'm': break;                                 /* parsed, never used (wtext.c:424-425; the filters are commented out of the usage) */
-			case 1001: o->gpu = atoi(optarg); break;
-			case 1002: o->pool_gb = (uint64_t)atoll(optarg); break;
-			case 1003: o->block = (uint32_t)atoi(optarg); if(o->block < 1) o->block = 1; break;
-			default: return 1;
+			default: if(!ht_devopt(&o->dev, c, optarg)) return 1; if(c == 1003){ o->block = (uint32_t)o->dev.block; if(o->block < 1) o->block = 1; }
 		}
 	}
 	if(o->pbs.n == 0 || o->ovls.n == 0 || o->output == NULL) return 1;

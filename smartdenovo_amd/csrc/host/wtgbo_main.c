@@ -20,25 +20,17 @@
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
-#include <pthread.h>
 #include "wtgbo_core.h"
-
-#define DIE_WTZ(rc, what) do { if((rc) != WTZ_OK){ fprintf(stderr, " -- %s failed: %s --\n", what, wtz_last_error()); fflush(NULL); _exit(1); } } while(0)
+#define HT_EXIT() GBO_DIE()
+#include "wtz_tool.h"
 
 typedef struct {
 	wtz_ctx_t *ctx; uint32_t n_rd; int zindex_all;
 	uint32_t *pq, *pc, *itp, *ids; uint8_t *itd; wtz_pair_summary_t *sum; wtz_aln_result_t *aln; uint32_t cap;
 	uint32_t *cig; uint64_t capcig;
 	uint8_t *mark;            /* per uploaded read: in the current z-index subset */
+	gbo_t *G; const gbo_job_t *jobs; gbo_res_t *res;      /* the jobs in hand (gbo_align_jobs) */
 } gbo_dev_t;
-
-typedef struct { const wtz_params_c *P; int device; uint64_t pool_bytes; wtz_ctx_t *ctx; int rc; char err[256]; pthread_t th; } gbo_ctxjob_t;
-static void *gbo_ctxjob_main(void *arg){
-	gbo_ctxjob_t *j = (gbo_ctxjob_t*)arg;
-	j->rc = wtz_ctx_create(j->device, j->P, j->pool_bytes, &j->ctx);
-	if(j->rc != WTZ_OK) snprintf(j->err, sizeof j->err, "%s", wtz_last_error());
-	return NULL;
-}
 
 /* 0 = done, 1 = the scratch pool was too small for this many pairs */
 static int gbo_align_range(gbo_t *G, gbo_dev_t *D, const gbo_job_t *jobs, uint32_t n, gbo_res_t *res){
@@ -59,17 +51,17 @@ static int gbo_align_range(gbo_t *G, gbo_dev_t *D, const gbo_job_t *jobs, uint32
 		for(uint32_t i = 0; i < k; i++) D->mark[D->ids[i]] = 0;
 		/* ascending order */
 		for(uint32_t gap = k / 2; gap > 0; gap /= 2) for(uint32_t i = gap; i < k; i++){ uint32_t v = D->ids[i], j = i; while(j >= gap && D->ids[j - gap] > v){ D->ids[j] = D->ids[j - gap]; j -= gap; } D->ids[j] = v; }
-		rc = wtz_zindex_build_subset(D->ctx, D->ids, k); if(rc == WTZ_E_POOL) return 1; DIE_WTZ(rc, "wtz_zindex_build_subset");
+		rc = wtz_zindex_build_subset(D->ctx, D->ids, k); if(rc == WTZ_E_POOL) return 1; if(rc != WTZ_OK) ht_die("wtz_zindex_build_subset");
 	}
-	rc = wtz_batch_begin(D->ctx); DIE_WTZ(rc, "wtz_batch_begin");
-	rc = wtz_pairs_seed(D->ctx, D->pq, D->pc, n, D->sum); if(rc == WTZ_E_POOL) return 1; DIE_WTZ(rc, "wtz_pairs_seed");
+	rc = wtz_batch_begin(D->ctx); if(rc != WTZ_OK) ht_die("wtz_batch_begin");
+	rc = wtz_pairs_seed(D->ctx, D->pq, D->pc, n, D->sum); if(rc == WTZ_E_POOL) return 1; if(rc != WTZ_OK) ht_die("wtz_pairs_seed");
 	uint32_t m = 0;
 	for(uint32_t i = 0; i < n; i++) if(D->sum[i].gate && D->sum[i].nwin[0]){ D->itp[m] = i; D->itd[m] = 0; m++; }      /* hzm_aln.h:1698-1699: windows, chain >= -R */
 	if(m == 0) return 0;
-	rc = wtz_pairs_align(D->ctx, D->itp, D->itd, m, D->aln); if(rc == WTZ_E_POOL) return 1; DIE_WTZ(rc, "wtz_pairs_align");
+	rc = wtz_pairs_align(D->ctx, D->itp, D->itd, m, D->aln); if(rc == WTZ_E_POOL) return 1; if(rc != WTZ_OK) ht_die("wtz_pairs_align");
 	uint64_t tot = 0; for(uint32_t k = 0; k < m; k++) tot += D->aln[k].cigar_len;
 	if(tot + 1 > D->capcig){ D->capcig = tot + 1 + tot / 2; D->cig = (uint32_t*)hx_realloc(D->cig, 4 * D->capcig); }
-	rc = wtz_fetch_cigars(D->ctx, D->cig, tot); if(rc == WTZ_E_POOL) return 1; DIE_WTZ(rc, "wtz_fetch_cigars");
+	rc = wtz_fetch_cigars(D->ctx, D->cig, tot); if(rc == WTZ_E_POOL) return 1; if(rc != WTZ_OK) ht_die("wtz_fetch_cigars");
 	uint32_t *dst = gbo_cigar_space(G, tot);
 	memcpy(dst, D->cig, 4 * (size_t)tot);
 	const uint64_t base = (uint64_t)(dst - G->cigar_pool);
@@ -83,20 +75,17 @@ static int gbo_align_range(gbo_t *G, gbo_dev_t *D, const gbo_job_t *jobs, uint32
 	return 0;
 }
 
+static int gbo_align_call(void *user, uint32_t at, uint32_t step){
+	gbo_dev_t *D = (gbo_dev_t*)user;
+	const uint64_t ncig0 = D->G->ncig;
+	if(!gbo_align_range(D->G, D, D->jobs + at, step, D->res + at)) return WTZ_OK;
+	D->G->ncig = ncig0;
+	return WTZ_E_POOL;
+}
 static void gbo_align_jobs(gbo_t *G, const gbo_job_t *jobs, size_t n, gbo_res_t *res){
 	gbo_dev_t *D = (gbo_dev_t*)G->backend;
-	size_t at = 0, step = n;
-	while(at < n){
-		if(step > n - at) step = n - at;
-		const uint64_t ncig0 = G->ncig;
-		if(gbo_align_range(G, D, jobs + at, (uint32_t)step, res + at)){
-			G->ncig = ncig0;
-			if(step == 1){ fprintf(stderr, " -- scratch pool too small even for one pair: %s --\n", wtz_last_error()); fflush(NULL); _exit(1); }
-			step = (step + 1) / 2;
-			continue;
-		}
-		at += step;
-	}
+	D->G = G; D->jobs = jobs; D->res = res;
+	ht_halving((uint32_t)n, gbo_align_call, D, "wtgbo alignment", "pair", 0);
 }
 
 int main(int argc, char **argv){
@@ -104,20 +93,16 @@ int main(int argc, char **argv){
 	if(gbo_parse_args(&G->O, argc, argv)) return gbo_usage();
 	gbo_opt_t *o = &G->O;
 	if(o->zsize < 5 || o->zsize > 16){ fprintf(stderr, " -- -z must be within 5..16 --\n"); return gbo_usage(); }
-	if(wtz_device_count() <= 0){ fprintf(stderr, " -- no HIP device visible: wtgbo (MI355X build) has no CPU path for the alignment: %s --\n", wtz_last_error()); return 1; }
+	if(ht_no_device("wtgbo", "alignment")) return 1;
 	/* the context - above all the hipMalloc of its scratch pool, ~35 ms per GB - is created on a helper thread while the reads are loaded.  Default pool 16 GB, not the
 	 * library's 45 % of the HBM: a pass aligns thousands of pairs, not hundreds of thousands (E. coli shape: 5.4 s wall with the 128 GB default, 1.0 s with 16 GB) */
-	wtz_params_c P; memset(&P, 0, sizeof P);
-	P.ksize = 16; P.zsize = (uint32_t)o->zsize; P.hk = 1; P.hz = (uint32_t)o->hz; P.ksave = 4; P.kovl = 300; P.ncand = 500; P.nbest = 100;
-	P.kwin = (uint32_t)o->kwin; P.kstep = (uint32_t)o->kstep; P.ztot = (uint32_t)o->zovl; P.zovl = (uint32_t)o->zovl;
-	P.max_kmer_freq = 0; P.max_zmer_freq = (uint32_t)o->zcut; P.max_kmer_var = (uint32_t)o->kvar;
-	P.win_rep_norm = 20; P.win_rep_cutoff = 100;
+	wtz_params_c P; ht_default_params(&P);
+	P.zsize = (uint32_t)o->zsize; P.hz = (uint32_t)o->hz; P.kwin = (uint32_t)o->kwin; P.kstep = (uint32_t)o->kstep; P.ztot = (uint32_t)o->zovl; P.zovl = (uint32_t)o->zovl;
+	P.max_zmer_freq = (uint32_t)o->zcut; P.max_kmer_var = (uint32_t)o->kvar;
 	P.w = o->w; P.ew = o->ew; P.W = o->W; P.M = o->M; P.X = o->X; P.O = o->O; P.E = o->E; P.T = o->T;
 	P.min_score = o->min_score; P.min_id = o->min_id;
-	P.dot_matrix = 0; P.xvar = 128; P.yvar = 64; P.min_block_len = 160; P.max_overhang = 256; P.deviation_penalty = 1.0f; P.gap_penalty = 0.05f;
 	P.refine = o->refine; P.aux_strand = 1;      /* -n: the device applies the gates of hzm_aln.h:1715-1718 before it refines (wtz_task_refine) */
-	static gbo_ctxjob_t cj; cj.P = &P; cj.device = o->gpu; cj.pool_bytes = (o->pool_gb ? o->pool_gb : 16) << 30; cj.ctx = NULL; cj.rc = WTZ_OK;
-	const int cj_started = (pthread_create(&cj.th, NULL, gbo_ctxjob_main, &cj) == 0);
+	static ht_ctxjob_t cj; ht_ctxjob_start(&cj, &P, o->gpu, (o->pool_gb ? o->pool_gb : 16) << 30);
 	G->st.keep_text = (o->ingest_host == 0);
 	gbo_load_inputs(G);            /* its error paths leave through exit(): join first if that ever matters - they fire within milliseconds of the start */
 	/* ---- device: every read and its reverse complement.  The bases travel as text and are packed on the device (wtz_upload_reads_ascii),
@@ -128,16 +113,14 @@ int main(int argc, char **argv){
 	for(uint32_t i = 0; i < n; i++){ rdoff[i] = G->st.reads[i].off; tot += G->st.reads[i].len; }
 	gbo_dev_t D; memset(&D, 0, sizeof D);
 	D.n_rd = n;
-	if(cj_started) pthread_join(cj.th, NULL); else gbo_ctxjob_main(&cj);
-	if(cj.rc != WTZ_OK){ fprintf(stderr, " -- wtz_ctx_create failed: %s --\n", cj.err); fflush(NULL); _exit(1); }
-	D.ctx = cj.ctx;
+	D.ctx = ht_ctxjob_join(&cj);
 	int rc;
-	if(G->st.keep_text){ rc = wtz_upload_reads_ascii(D.ctx, G->st.text, G->st.nbase, rdoff, G->rdlen, n, 0, NULL); DIE_WTZ(rc, "wtz_upload_reads_ascii"); free(G->st.text); G->st.text = NULL; }
-	else { rc = wtz_upload_reads(D.ctx, G->st.bits, (G->st.nbase + 31) >> 5, rdoff, G->rdlen, n); DIE_WTZ(rc, "wtz_upload_reads"); }
-	rc = wtz_append_revcomp_views(D.ctx); DIE_WTZ(rc, "wtz_append_revcomp_views");
+	if(G->st.keep_text){ rc = wtz_upload_reads_ascii(D.ctx, G->st.text, G->st.nbase, rdoff, G->rdlen, n, 0, NULL); if(rc != WTZ_OK) ht_die("wtz_upload_reads_ascii"); free(G->st.text); G->st.text = NULL; }
+	else { rc = wtz_upload_reads(D.ctx, G->st.bits, (G->st.nbase + 31) >> 5, rdoff, G->rdlen, n); if(rc != WTZ_OK) ht_die("wtz_upload_reads"); }
+	rc = wtz_append_revcomp_views(D.ctx); if(rc != WTZ_OK) ht_die("wtz_append_revcomp_views");
 	free(rdoff);
 	D.zindex_all = o->zindex_batch < 0 ? (2 * tot <= 2400000000ull) : !o->zindex_batch;      /* 16 B per indexed base: all reads while that stays under ~40 GB */
-	if(D.zindex_all){ rc = wtz_zindex_build(D.ctx); DIE_WTZ(rc, "wtz_zindex_build"); }
+	if(D.zindex_all){ rc = wtz_zindex_build(D.ctx); if(rc != WTZ_OK) ht_die("wtz_zindex_build"); }
 	else D.mark = (uint8_t*)calloc((size_t)n * 2 + 1, 1);
 	fprintf(stderr, "[wtgbo-mi355x] %u reads, %llu bp (+ reverse complements) on device %d, z-mer index %s\n", n, (unsigned long long)tot, o->gpu, D.zindex_all ? "of all reads" : "per batch");
 	G->backend = &D;

@@ -13,9 +13,10 @@
  *   wtz_lib_pairs.h                wtz_pairs_seed, wtz_pairs_windows
  *   wtz_lib_align.h                wtz_pairs_align: lane pipelines, chained K-sw1, K-sw2, K-sw3 extension jobs, fused stitch
  *   wtz_lib_fetch.h                CIGAR fetch and text rendering
- *   wtz_lib_batch.h                wtz_extend_batch, wtz_local_batch, wtz_kext_batch, wtz_align_batch, the test-only wtz_test_dp
- *   wtz_lib_glob.h                 wtz_global_batch, wtz_alignx_batch (included by wtz_lib_batch.h)
+ *   wtz_lib_batch.h                the skeleton of the batch services, each step once; wtz_extend_batch, wtz_local_batch, wtz_kext_batch, wtz_align_batch
+ *   wtz_lib_glob.h                 wtz_global_batch, wtz_alignx_batch and the CIGAR hand-out they share (included by wtz_lib_batch.h)
  *   wtz_lib_pwtext.h               wtz_pwtext_batch (included by wtz_lib_batch.h)
+ *   wtz_testdp.h                   the test-only wtz_test_dp (included by wtz_lib_batch.h)
  *
  * Execution model: every stage is a flat grid of independent tasks (one lane, wavefront or workgroup per read / query / pair /
  * window), 64-thread workgroups so that each wave is scheduled on its own and the thousands of waves per launch spread over all

@@ -1,8 +1,94 @@
 /*
  * wtz_lib_batch.h — the DP routines as batch services for callers that hold their own problems: wtz_extend_batch (K-sw3), wtz_local_batch (K-local),
- * wtz_kext_batch (K-kext), wtz_align_batch (K-local + K-kext), through wtz_lib_glob.h wtz_global_batch (K-glob) and wtz_alignx_batch (all three) and, through wtz_lib_pwtext.h wtz_pwtext_batch (K-pwtext) and, through
- * wtz_testdp.h, the test-only wtz_test_dp.  Included by wtz_lib.cpp.
+ * wtz_kext_batch (K-kext), wtz_align_batch (K-local + K-kext), through wtz_lib_glob.h wtz_global_batch (K-glob) and wtz_alignx_batch (all three), through
+ * wtz_lib_pwtext.h wtz_pwtext_batch (K-pwtext) and, through wtz_testdp.h, the test-only wtz_test_dp.  Included by wtz_lib.cpp.
+ *
+ * The skeleton they are written against stands first, each step once: BATCH_ARGS / batch_count / batch_begin (a call before it looks at a problem), batch_scores,
+ * batch_order, batch_upload / batch_fetch (the two ends of a launch group), form_dispatch / for_each_form, pack_runs, pool_fail, batch_leave.
  */
+/* WTZ_E_POOL from a request the host planned itself; kind as wtz_pool_failure_kind reports it (1 = main pool) */
+static int pool_fail(wtz_ctx *c, int kind, const char *fmt, ...){
+	va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap);
+	c->last_pool_fail = kind; return WTZ_E_POOL;
+}
+/* nothing of a call lives on: the main pool goes back empty (wtz_pool_info shows main_used = 0; the bytes taken are in counters.pool_peak) */
+static int batch_leave(wtz_ctx *c){ CHK(pool_reset(c)); c->main_used_call = 0; return WTZ_OK; }
+/* one block per item */
+static int batch_count(uint32_t n, const char *who, const char *items){ return n > 0x7FFFFFFFu ? wtz_fail(WTZ_E_ARG, "%s: more than 2^31 - 1 %s in one call", who, items) : WTZ_OK; }
+/* the checks every entry point starts with, in the order a caller sees them; n == 0 is WTZ_OK whatever the other arguments are (BATCH_ARGS returns on it too).
+ * args_ok: no argument of the call is a null pointer that must not be one; who: NULL for the entry points without a limit on n */
+#define BATCH_ARGS(c, n, args_ok, who, items) do { const int rc_ = batch_args(c, n, args_ok, who, items); if(rc_ != WTZ_OK || (n) == 0) return rc_; } while(0)
+static int batch_args(const wtz_ctx *c, uint32_t n, bool args_ok, const char *who, const char *items){
+	if(!c || !c->bits) return wtz_fail(WTZ_E_ARG, "reads not uploaded");
+	if(n == 0) return WTZ_OK;
+	if(!args_ok) return wtz_fail(WTZ_E_ARG, "null argument");
+	return who ? batch_count(n, who, items) : WTZ_OK;
+}
+/* behind CTX_ENTER, once all arguments that are not problems are checked: empty pools and THE fetch of the reads' offsets of the call */
+static int batch_begin(wtz_ctx *c, std::vector<uint64_t> &h_off){
+	CHK(pool_reset(c)); h_off.resize(c->n_reads);
+	return dev_d2h(h_off.data(), c->rdoff, (size_t)c->n_reads * 8);
+}
+/* the value range of the 16-bit routines, or WTZ_E_ARG: scores as the reference's int8 matrix holds them (kswx.h:1495-1520 fills it from M / X), gap opening costs >= 0
+ * (ksw.c:253-256; an opening cost of 0 is a setting like any other), gap extension costs >= min_ext: 1 where the routine divides by them (ksw.c:403-406), else 0 */
+static int batch_scores(const wtz_ctx *c, const char *who, int32_t o_del, int32_t e_del, int32_t o_ins, int32_t e_ins, int32_t min_ext){
+	if(c->P.M < 1 || c->P.M > 127 || c->P.X > 0 || c->P.X < -128) return wtz_fail(WTZ_E_ARG, "%s: M must be in [1, 127] and X in [-128, 0]", who);
+	if(o_del < 0 || o_ins < 0 || e_del < min_ext || e_ins < min_ext || (int64_t)o_del + e_del > 32767 || (int64_t)o_ins + e_ins > 32767)
+		return wtz_fail(WTZ_E_ARG, min_ext ? "%s: gap opening costs must be >= 0, gap extension costs >= 1 and open + extend <= 32767" : "%s: gap costs must be >= 0 and open + extend <= 32767", who);
+	return WTZ_OK;
+}
+/* the order of a launch: by form (NULL: one form), widest first, and inside a form by weight, largest first; equal problems keep their order */
+static std::vector<uint32_t> batch_order(uint32_t n, const uint32_t *form, const std::vector<uint64_t> &weight){
+	std::vector<uint32_t> order(n);
+	for(uint32_t i = 0; i < n; i++) order[i] = i;
+	std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b){ if(form && form[a] != form[b]) return form[a] > form[b]; return weight[a] > weight[b]; });
+	return order;
+}
+/* the problems, their order (d_order == NULL: none) and zeroed results on the device, from the arena scope of the caller */
+template<typename P, typename R> static int batch_upload(const std::vector<P> &hp, const std::vector<uint32_t> &order, P **d_pr, uint32_t **d_order, R **d_res){
+	const size_t n = hp.size();
+	CHK(dev_alloc((void**)d_pr, n * sizeof(P))); CHK(dev_h2d(*d_pr, hp.data(), n * sizeof(P)));
+	if(d_order){ CHK(dev_alloc((void**)d_order, n * 4)); CHK(dev_h2d(*d_order, order.data(), n * 4)); }
+	CHK(dev_alloc((void**)d_res, n * sizeof(R))); CHK(dev_set(*d_res, 0, n * sizeof(R)));
+	return WTZ_OK;
+}
+/* the end of a launch group that began with batch_upload and tm.start(): one synchronisation, the kernel time to ms, the results back into hr */
+template<typename R> static int batch_fetch(wtz_timer &tm, double &ms, size_t n, const R *d_res, std::vector<R> &hr){
+	CHK(dev_sync()); ms += tm.stop(); hr.resize(n);
+	return dev_d2h(hr.data(), d_res, n * sizeof(R));
+}
+/* the run-time form (slots per lane: 1, 2, 4, 8, 16, 32) as a compile-time constant: f(std::integral_constant<int, C>()) */
+template<typename F> static int form_dispatch(uint32_t C, F f){
+	switch(C){
+		case 1: return f(std::integral_constant<int, 1>());
+		case 2: return f(std::integral_constant<int, 2>());
+		case 4: return f(std::integral_constant<int, 4>());
+		case 8: return f(std::integral_constant<int, 8>());
+		case 16: return f(std::integral_constant<int, 16>());
+		default: return f(std::integral_constant<int, 32>());
+	}
+}
+/* one call per form present among the n problems form_of(0 .. n - 1) (sorted by form): f(form constant, b0, b1) for the stretch [b0, b1) */
+template<typename FORM, typename F> static int for_each_form(uint32_t n, FORM form_of, F f){
+	for(uint32_t b0 = 0, b1; b0 < n; b0 = b1){
+		const uint32_t C = form_of(b0);
+		for(b1 = b0 + 1; b1 < n && form_of(b1) == C; b1++){}
+		CHK(form_dispatch(C, [&](auto K){ return f(K, b0, b1); }));
+	}
+	return WTZ_OK;
+}
+/* the run lists of off.size() - 1 problems (off[t]: the words in front of list t, off.back(): all; src(t): where list t lies on the device) packed on the device and fetched in one copy to dst[0, off.back()) */
+template<typename TAG, typename SRC> static int pack_runs(const std::vector<uint64_t> &off, SRC src, uint32_t *dst){
+	const size_t n = off.size() - 1; const uint64_t tot = off[n];
+	if(tot == 0) return WTZ_OK;
+	uint64_t *d_off = NULL; uint32_t *d_flat = NULL;
+	CHK(dev_alloc((void**)&d_off, (n + 1) * 8)); CHK(dev_h2d(d_off, off.data(), (n + 1) * 8));
+	CHK(dev_alloc((void**)&d_flat, (size_t)tot * 4));
+	CHK(wtz_launch<TAG>(n, [=] WTZ_LAMBDA (uint64_t t){ const uint64_t o = d_off[t], e = d_off[t + 1]; const uint32_t *s = src(t); for(uint64_t k = o; k < e; k++) d_flat[k] = s[k - o]; }));
+	CHK(dev_sync());
+	return dev_d2h(dst, d_flat, (size_t)tot * 4);
+}
+
 /* the two sides of problem i as views of the uploaded reads (h_off: the reads' offsets, fetched by the caller), or WTZ_E_ARG.  allow_empty: a side of
  * length 0 is a problem like any other (its start is not looked at); max_len > 0: the longest side the caller's kernel takes */
 static int dp_problem_views(const wtz_ctx *c, const std::vector<uint64_t> &h_off, const wtz_dp_problem_t &p, uint32_t i, bool allow_empty, int32_t max_len, wtz_seq_packed *q, wtz_seq_packed *t){
@@ -28,13 +114,9 @@ static int dp_problem_views(const wtz_ctx *c, const std::vector<uint64_t> &h_off
  * dispatch as the ends of wtzmo's stitched alignments (run_extjobs: register DP on one wavefront per job, LDS-ring and scalar forms for what is
  * outside their envelope).  out[i]: the kswx_t of the call + where its CIGAR words (traceback order reversed: first operation first) start in `cigar`. */
 extern "C" int wtz_extend_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32_t n, wtz_dp_result_t *out, uint32_t *cigar, uint64_t cigar_cap){
-	if(!c || !c->bits) return wtz_fail(WTZ_E_ARG, "reads not uploaded");
-	if(n == 0) return WTZ_OK;
-	if(!pr || !out || (!cigar && cigar_cap)) return wtz_fail(WTZ_E_ARG, "null argument");
+	BATCH_ARGS(c, n, pr && out && (cigar || !cigar_cap), NULL, NULL);
 	CTX_ENTER(c);
-	CHK(pool_reset(c));
-	std::vector<uint64_t> h_off(c->n_reads);
-	CHK(dev_d2h(h_off.data(), c->rdoff, (size_t)c->n_reads * 8));
+	std::vector<uint64_t> h_off; CHK(batch_begin(c, h_off));
 	std::vector<wtz_extjob_t> jobs(n);
 	for(uint32_t i = 0; i < n; i++){
 		const wtz_dp_problem_t &p = pr[i];
@@ -51,23 +133,15 @@ extern "C" int wtz_extend_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32
 	c->cnt.ms_stitch += tm.stop();
 	CHK(tpool_check(c, "wtz_extend_batch"));
 	CHK(dev_d2h(jobs.data(), d_jobs, (size_t)n * sizeof(wtz_extjob_t)));
-	std::vector<uint64_t> off((size_t)n + 1); uint64_t tot = 0;
+	std::vector<uint64_t> off((size_t)n + 1, 0);
 	for(uint32_t i = 0; i < n; i++){
-		if(jobs[i].bad) return wtz_fail(WTZ_E_POOL, "wtz_extend_batch: problem %u ran out of scratch", i);
-		const bool empty = jobs[i].qlen <= 0 || jobs[i].tlen <= 0;
-		off[i] = tot; tot += empty ? 0 : jobs[i].cigar_len;
+		if(jobs[i].bad) return wtz_fail(WTZ_E_POOL, "wtz_extend_batch: problem %u ran out of scratch", i);      /* the kind stays what the call before left */
+		off[i + 1] = off[i] + ((jobs[i].qlen <= 0 || jobs[i].tlen <= 0) ? 0 : jobs[i].cigar_len);
 		c->cnt.cells_shift += jobs[i].cells;
 	}
-	off[n] = tot;
+	const uint64_t tot = off[n];
 	if(tot > cigar_cap) return wtz_fail(WTZ_E_ARG, "wtz_extend_batch: CIGAR buffer too small (%llu words needed)", (unsigned long long)tot);
-	if(tot){
-		uint64_t *d_off = NULL; uint32_t *d_flat = NULL;
-		CHK(dev_alloc((void**)&d_off, ((size_t)n + 1) * 8)); CHK(dev_h2d(d_off, off.data(), ((size_t)n + 1) * 8));
-		CHK(dev_alloc((void**)&d_flat, (size_t)tot * 4));
-		CHK(wtz_launch<K_extcopy>(n, [=] WTZ_LAMBDA (uint64_t t){ const uint64_t o = d_off[t], e = d_off[t + 1]; const uint32_t *src = d_jobs[t].cigar; for(uint64_t k = o; k < e; k++) d_flat[k] = src[k - o]; }));
-		CHK(dev_sync());
-		CHK(dev_d2h(cigar, d_flat, (size_t)tot * 4));
-	}
+	CHK(pack_runs<K_extcopy>(off, [=] WTZ_LAMBDA (uint64_t t) -> const uint32_t* { return d_jobs[t].cigar; }, cigar));
 	for(uint32_t i = 0; i < n; i++){
 		wtz_dp_result_t o; memset(&o, 0, sizeof o);
 		const wtz_extjob_t &j = jobs[i];
@@ -87,39 +161,23 @@ extern "C" int wtz_extend_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32
 /* ksw_align2(..., KSW_XSTART) with 16-bit lanes (ksw.c:344-366 over ksw_i16, ksw.c:233-335) for n independent problems on views of the uploaded reads:
  * K-local (wtz_sw_local.h), one wavefront per problem, both passes on the same wavefront, largest problem first.  The strip-boundary column of a
  * problem (two buffers of t_len words, only for queries of more than one strip) is planned on the host and taken from the main pool in one block. */
-extern "C" int wtz_local_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32_t n, int32_t o_del, int32_t e_del, int32_t o_ins, int32_t e_ins, wtz_local_result_t *out){
-	if(!c || !c->bits) return wtz_fail(WTZ_E_ARG, "reads not uploaded");
-	if(n == 0) return WTZ_OK;
-	if(!pr || !out) return wtz_fail(WTZ_E_ARG, "null argument");
-	if(n > 0x7FFFFFFFu) return wtz_fail(WTZ_E_ARG, "wtz_local_batch: more than 2^31 - 1 problems in one call");      /* one block per problem */
-	/* the value range of the 16-bit routine: scores as the reference's int8 matrix holds them (kswx.h:1495-1520 fills it from M / X), gap costs >= 0 (ksw.c:253-256) */
-	if(c->P.M < 1 || c->P.M > 127 || c->P.X > 0 || c->P.X < -128) return wtz_fail(WTZ_E_ARG, "wtz_local_batch: M must be in [1, 127] and X in [-128, 0]");
-	if(o_del < 0 || e_del < 0 || o_ins < 0 || e_ins < 0 || (int64_t)o_del + e_del > 32767 || (int64_t)o_ins + e_ins > 32767) return wtz_fail(WTZ_E_ARG, "wtz_local_batch: gap costs must be >= 0 and open + extend <= 32767");
-	CTX_ENTER(c);
-	CHK(pool_reset(c));
-	std::vector<uint64_t> h_off(c->n_reads);
-	CHK(dev_d2h(h_off.data(), c->rdoff, (size_t)c->n_reads * 8));
-	std::vector<wtz_locprob_t> hp(n);
+static int local_run(wtz_ctx *c, const std::vector<uint64_t> &h_off, const wtz_dp_problem_t *pr, uint32_t n, int32_t o_del, int32_t e_del, int32_t o_ins, int32_t e_ins, wtz_local_result_t *out){
+	wtz_arena_scope launch_scope(&c->arena);      /* the buffers of the launch go back when it returns (scopes nest) */
+	std::vector<wtz_locprob_t> hp(n); std::vector<uint64_t> area(n);
 	unsigned long long bnd_words = 0;
 	for(uint32_t i = 0; i < n; i++){
 		const wtz_dp_problem_t &p = pr[i];
 		wtz_locprob_t d; CHK(dp_problem_views(c, h_off, p, i, false, WTZ_LOC_MAXLEN, &d.q, &d.t)); d.qlen = p.q_len; d.tlen = p.t_len; d.bnd_off = bnd_words;
 		if(p.q_len > wtz_loc_strip_cols(p.q_len)) bnd_words += 2ull * (unsigned long long)p.t_len;      /* more than one strip: on the device, more than 1 024 columns */
-		hp[i] = d;
+		hp[i] = d; area[i] = (uint64_t)p.q_len * (uint64_t)p.t_len;
 	}
-	std::vector<uint32_t> order(n);
-	for(uint32_t i = 0; i < n; i++) order[i] = i;
-	std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b){ return (uint64_t)hp[a].qlen * (uint64_t)hp[a].tlen > (uint64_t)hp[b].qlen * (uint64_t)hp[b].tlen; });
-	wtz_locprob_t *d_pr = NULL; uint32_t *d_order = NULL; wtz_locres_t *d_res = NULL; uint32_t *d_bnd = NULL;
-	CHK(dev_alloc((void**)&d_pr, (size_t)n * sizeof(wtz_locprob_t))); CHK(dev_h2d(d_pr, hp.data(), (size_t)n * sizeof(wtz_locprob_t)));
-	CHK(dev_alloc((void**)&d_order, (size_t)n * 4)); CHK(dev_h2d(d_order, order.data(), (size_t)n * 4));
-	CHK(dev_alloc((void**)&d_res, (size_t)n * sizeof(wtz_locres_t))); CHK(dev_set(d_res, 0, (size_t)n * sizeof(wtz_locres_t)));
+	wtz_locprob_t *d_pr = NULL; uint32_t *d_order = NULL; wtz_locres_t *d_res = NULL;
+	CHK(batch_upload(hp, batch_order(n, NULL, area), &d_pr, &d_order, &d_res));
+	uint32_t *d_bnd = NULL;
 	if(bnd_words){
-		if(bnd_words * 4ull > c->main_bytes){ c->last_pool_fail = 1; return wtz_fail(WTZ_E_POOL, "wtz_local_batch: %llu bytes of strip boundaries in a main pool of %llu; use fewer problems per call or a larger pool", bnd_words * 4ull, (unsigned long long)c->main_bytes); }
-		if(pool_alloc_host(c, 0, (size_t)bnd_words * 4, (void**)&d_bnd) != WTZ_OK){      /* the pool's own rounding on top of a request that just fitted */
-			c->last_pool_fail = 1;
-			return wtz_fail(WTZ_E_POOL, "wtz_local_batch: no room for %llu bytes of strip boundaries in the main pool; use fewer problems per call or a larger pool", bnd_words * 4ull);
-		}
+		if(bnd_words * 4ull > c->main_bytes) return pool_fail(c, 1, "wtz_local_batch: %llu bytes of strip boundaries in a main pool of %llu; use fewer problems per call or a larger pool", bnd_words * 4ull, (unsigned long long)c->main_bytes);
+		if(pool_alloc_host(c, 0, (size_t)bnd_words * 4, (void**)&d_bnd) != WTZ_OK)      /* the pool's own rounding on top of a request that just fitted */
+			return pool_fail(c, 1, "wtz_local_batch: no room for %llu bytes of strip boundaries in the main pool; use fewer problems per call or a larger pool", bnd_words * 4ull);
 	}
 	wtz_locsc_t S; S.M = c->P.M; S.X = c->P.X; S.oe_del = o_del + e_del; S.e_del = e_del; S.oe_ins = o_ins + e_ins; S.e_ins = e_ins;
 	wtz_timer tm; tm.start();
@@ -128,10 +186,8 @@ extern "C" int wtz_local_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32_
 #else
 	for(uint32_t b = 0; b < n; b++){ const uint32_t id = d_order[b]; wtz_local_problem(d_pr[id], S, d_bnd, d_res[id]); }
 #endif
-	CHK(dev_sync());
-	c->cnt.ms_local += tm.stop();
-	std::vector<wtz_locres_t> hr(n);
-	CHK(dev_d2h(hr.data(), d_res, (size_t)n * sizeof(wtz_locres_t)));
+	std::vector<wtz_locres_t> hr;
+	CHK(batch_fetch(tm, c->cnt.ms_local, n, d_res, hr));
 	for(uint32_t i = 0; i < n; i++){
 		wtz_local_result_t o; memset(&o, 0, sizeof o);
 		o.score = hr[i].score; o.te = hr[i].te; o.qe = hr[i].qe; o.tb = hr[i].tb; o.qb = hr[i].qb; o.form_used = hr[i].form; o.cells = hr[i].cells;
@@ -140,20 +196,22 @@ extern "C" int wtz_local_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32_
 	}
 	c->cnt.n_local += n;
 	CHK(pool_check(c, "wtz_local_batch"));
-	/* nothing of the call lives on: the main pool goes back empty (wtz_pool_info shows main_used = 0; the bytes taken are in counters.pool_peak) */
-	CHK(pool_reset(c));
-	c->main_used_call = 0;
-	return WTZ_OK;
+	return batch_leave(c);
+}
+extern "C" int wtz_local_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32_t n, int32_t o_del, int32_t e_del, int32_t o_ins, int32_t e_ins, wtz_local_result_t *out){
+	BATCH_ARGS(c, n, pr && out, "wtz_local_batch", "problems");
+	CHK(batch_scores(c, "wtz_local_batch", o_del, e_del, o_ins, e_ins, 0));
+	CTX_ENTER(c);
+	std::vector<uint64_t> h_off; CHK(batch_begin(c, h_off));
+	return local_run(c, h_off, pr, n, o_del, e_del, o_ins, e_ins, out);
 }
 
 /* ------------------------------------------------------------------------------------------------ */
 /* ksw_extend2 as a batch service, and kswx_align_no_stat on top of it and of wtz_local_batch           */
 /* ------------------------------------------------------------------------------------------------ */
-/* the arguments every problem of a K-kext launch shares, or WTZ_E_ARG: scores as the reference's int8 matrix holds them, gap extensions >= 1 (ksw.c:403-406 divides by them) */
+/* the arguments every problem of a K-kext launch shares, or WTZ_E_ARG */
 static int kext_scores(const wtz_ctx *c, const char *who, int32_t o_del, int32_t e_del, int32_t o_ins, int32_t e_ins, int32_t zdrop, wtz_kextsc_t *S){
-	if(c->P.M < 1 || c->P.M > 127 || c->P.X > 0 || c->P.X < -128) return wtz_fail(WTZ_E_ARG, "%s: M must be in [1, 127] and X in [-128, 0]", who);
-	if(o_del < 0 || o_ins < 0 || e_del < 1 || e_ins < 1 || (int64_t)o_del + e_del > 32767 || (int64_t)o_ins + e_ins > 32767)
-		return wtz_fail(WTZ_E_ARG, "%s: gap opening costs must be >= 0, gap extension costs >= 1 and open + extend <= 32767", who);
+	CHK(batch_scores(c, who, o_del, e_del, o_ins, e_ins, 1));
 	S->M = c->P.M; S->X = c->P.X; S->o_del = o_del; S->e_del = e_del; S->o_ins = o_ins; S->e_ins = e_ins; S->zdrop = zdrop;
 	return WTZ_OK;
 }
@@ -173,14 +231,14 @@ static int kext_plan(const wtz_ctx *c, const std::vector<uint64_t> &h_off, const
 }
 static int32_t kext_slots(const wtz_kextprob_t &d){ return d.dlo + (d.w < d.qlen - 1 ? d.w : d.qlen - 1) + 1; }
 
+template<int C> static int kext_launch(const wtz_kextprob_t *pr, const uint32_t *order, uint32_t n, const wtz_kextsc_t &S, wtz_kextres_t *res){
 #ifdef WTZ_EMUL
-template<int C> static void kext_emul(const wtz_kextprob_t *pr, const uint32_t *order, uint32_t n, const wtz_kextsc_t &S, wtz_kextres_t *res){
 	for(uint32_t b = 0; b < n; b++) wtz_kext_problem<C>(pr[order[b]], S, res[order[b]]);
-}
-#define KEXT_LAUNCH(C) kext_emul<C>(d_pr, d_order + b0, b1 - b0, S, d_res)
 #else
-#define KEXT_LAUNCH(C) WTZ_LAUNCH(wtz_kernel_kext<C>, b1 - b0, 64, 0, g_stream, (const wtz_kextprob_t*)d_pr, (const uint32_t*)(d_order + b0), b1 - b0, S, d_res)
+	WTZ_LAUNCH(wtz_kernel_kext<C>, n, 64, 0, g_stream, pr, order, n, S, res);
 #endif
+	return WTZ_OK;
+}
 /* THE launch path of K-kext: the problems of one score setting, one launch per kernel instantiation present, one wavefront per problem, largest first.
  * hr[i], form[i]: result and slots per lane of problem i.  Counts into ms_kext / n_kext / cells_kext. */
 static int kext_run(wtz_ctx *c, const std::vector<wtz_kextprob_t> &hp, const wtz_kextsc_t &S, std::vector<wtz_kextres_t> &hr, std::vector<uint32_t> &form){
@@ -188,55 +246,25 @@ static int kext_run(wtz_ctx *c, const std::vector<wtz_kextprob_t> &hp, const wtz
 	hr.resize(n); form.resize(n);
 	if(n == 0) return WTZ_OK;
 	wtz_arena_scope launch_scope(&c->arena);      /* the buffers of this launch group go back when it returns (scopes nest) */
-	std::vector<uint32_t> order(n);
-	for(uint32_t i = 0; i < n; i++){ order[i] = i; form[i] = (uint32_t)wtz_kext_form(kext_slots(hp[i])); }
-	std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b){
-		if(form[a] != form[b]) return form[a] > form[b];
-		return (uint64_t)hp[a].tlen * (uint64_t)kext_slots(hp[a]) > (uint64_t)hp[b].tlen * (uint64_t)kext_slots(hp[b]); });
+	std::vector<uint64_t> weight(n);
+	for(uint32_t i = 0; i < n; i++){ form[i] = (uint32_t)wtz_kext_form(kext_slots(hp[i])); weight[i] = (uint64_t)hp[i].tlen * (uint64_t)kext_slots(hp[i]); }
+	const std::vector<uint32_t> order = batch_order(n, form.data(), weight);
 	wtz_kextprob_t *d_pr = NULL; uint32_t *d_order = NULL; wtz_kextres_t *d_res = NULL;
-	CHK(dev_alloc((void**)&d_pr, (size_t)n * sizeof(wtz_kextprob_t))); CHK(dev_h2d(d_pr, hp.data(), (size_t)n * sizeof(wtz_kextprob_t)));
-	CHK(dev_alloc((void**)&d_order, (size_t)n * 4)); CHK(dev_h2d(d_order, order.data(), (size_t)n * 4));
-	CHK(dev_alloc((void**)&d_res, (size_t)n * sizeof(wtz_kextres_t))); CHK(dev_set(d_res, 0, (size_t)n * sizeof(wtz_kextres_t)));
+	CHK(batch_upload(hp, order, &d_pr, &d_order, &d_res));
 	wtz_timer tm; tm.start();
-	for(uint32_t b0 = 0, b1; b0 < n; b0 = b1){
-		const uint32_t C = form[order[b0]];
-		for(b1 = b0 + 1; b1 < n && form[order[b1]] == C; b1++){}
-		switch(C){
-			case 1: KEXT_LAUNCH(1); break;
-			case 2: KEXT_LAUNCH(2); break;
-			case 4: KEXT_LAUNCH(4); break;
-			case 8: KEXT_LAUNCH(8); break;
-			case 16: KEXT_LAUNCH(16); break;
-			default: KEXT_LAUNCH(32); break;
-		}
-	}
-	CHK(dev_sync());
-	c->cnt.ms_kext += tm.stop();
-	CHK(dev_d2h(hr.data(), d_res, (size_t)n * sizeof(wtz_kextres_t)));
+	CHK(for_each_form(n, [&](uint32_t b){ return form[order[b]]; }, [&](auto K, uint32_t b0, uint32_t b1){ return kext_launch<decltype(K)::value>(d_pr, d_order + b0, b1 - b0, S, d_res); }));
+	CHK(batch_fetch(tm, c->cnt.ms_kext, n, d_res, hr));
 	for(uint32_t i = 0; i < n; i++) c->cnt.cells_kext += hr[i].cells;
 	c->cnt.n_kext += n;
-	return WTZ_OK;
-}
-#undef KEXT_LAUNCH
-/* the main pool goes back empty, as after wtz_local_batch */
-static int kext_leave(wtz_ctx *c, const char *who){
-	CHK(pool_check(c, who));
-	CHK(pool_reset(c));
-	c->main_used_call = 0;
 	return WTZ_OK;
 }
 
 /* ksw_extend2 (ksw.c:381-478) for n independent problems on views of the uploaded reads: K-kext (wtz_sw_kext.h) */
 extern "C" int wtz_kext_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32_t n, int32_t o_del, int32_t e_del, int32_t o_ins, int32_t e_ins, int32_t end_bonus, int32_t zdrop, wtz_kext_result_t *out){
-	if(!c || !c->bits) return wtz_fail(WTZ_E_ARG, "reads not uploaded");
-	if(n == 0) return WTZ_OK;
-	if(!pr || !out) return wtz_fail(WTZ_E_ARG, "null argument");
-	if(n > 0x7FFFFFFFu) return wtz_fail(WTZ_E_ARG, "wtz_kext_batch: more than 2^31 - 1 problems in one call");
+	BATCH_ARGS(c, n, pr && out, "wtz_kext_batch", "problems");
 	wtz_kextsc_t S; CHK(kext_scores(c, "wtz_kext_batch", o_del, e_del, o_ins, e_ins, zdrop, &S));
 	CTX_ENTER(c);
-	CHK(pool_reset(c));
-	std::vector<uint64_t> h_off(c->n_reads);
-	CHK(dev_d2h(h_off.data(), c->rdoff, (size_t)c->n_reads * 8));
+	std::vector<uint64_t> h_off; CHK(batch_begin(c, h_off));
 	std::vector<wtz_kextprob_t> hp(n);
 	for(uint32_t i = 0; i < n; i++) CHK(kext_plan(c, h_off, pr[i], i, S, end_bonus, &hp[i]));
 	std::vector<wtz_kextres_t> hr; std::vector<uint32_t> form;
@@ -247,16 +275,15 @@ extern "C" int wtz_kext_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32_t
 		o.form_used = form[i]; o.rows = hr[i].rows; o.cells = hr[i].cells;
 		out[i] = o;
 	}
-	return kext_leave(c, "wtz_kext_batch");
+	CHK(pool_check(c, "wtz_kext_batch"));
+	return batch_leave(c);
 }
 
 /* kswx_align_no_stat (kswx.h:1504-1511): the local hit of wtz_local_batch, then kswx_extend_core (kswx.h:1386-1441) as two stages of K-kext launches.
  * side 0 = left (the reversed prefixes in front of the hit), 1 = right; role 0 = the problem's target is ksw_extend2's target (rows), 1 = its query is. */
 /* the argument checks of wtz_align_batch, under the name of the entry point that makes them */
 static int align_args(const wtz_ctx *c, const char *who, const wtz_dp_problem_t *pr, uint32_t n, const void *out, int32_t w, int32_t I, int32_t D, int32_t E, int32_t T, wtz_kextsc_t *SR){
-	if(!c || !c->bits) return wtz_fail(WTZ_E_ARG, "reads not uploaded");
-	if(n == 0) return WTZ_OK;
-	if(!pr || !out) return wtz_fail(WTZ_E_ARG, "null argument");
+	BATCH_ARGS(c, n, pr && out, NULL, NULL);
 	if(I > 0 || D > 0 || E > -1 || I < -32767 || D < -32767 || E < -32767 || T < -(1 << 30)) return wtz_fail(WTZ_E_ARG, "%s: I and D must be <= 0 and E <= -1 (costs as negative numbers)", who);
 	if(w < 0 || w > WTZ_KEXT_MAXW) return wtz_fail(WTZ_E_ARG, "%s: band width %d outside [0, %d]", who, w, WTZ_KEXT_MAXW);
 	/* by role: kswx.h:1396 / 1422 and, with the opening costs exchanged, kswx.h:1407 / 1431 */
@@ -264,19 +291,21 @@ static int align_args(const wtz_ctx *c, const char *who, const wtz_dp_problem_t 
 	CHK(kext_scores(c, who, -I, -E, -D, -E, -1, &SR[1]));
 	return WTZ_OK;
 }
-static int align_stages(wtz_ctx *c, const char *entry, const wtz_dp_problem_t *pr, uint32_t n, int32_t w, int32_t I, int32_t D, int32_t E, int32_t T, const wtz_kextsc_t *SR, wtz_align_result_t *out);
+static int align_stages(wtz_ctx *c, const char *entry, const std::vector<uint64_t> &h_off, const wtz_dp_problem_t *pr, uint32_t n, int32_t w, int32_t I, int32_t D, int32_t E, int32_t T, const wtz_kextsc_t *SR, wtz_align_result_t *out);
 extern "C" int wtz_align_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32_t n, int32_t w, int32_t I, int32_t D, int32_t E, int32_t T, wtz_align_result_t *out){
 	wtz_kextsc_t SR[2];
 	CHK(align_args(c, "wtz_align_batch", pr, n, out, w, I, D, E, T, SR));
 	if(n == 0) return WTZ_OK;
+	CHK(batch_count(n, "wtz_local_batch", "problems"));      /* stage 1's limit, under its name */
 	CTX_ENTER(c);
-	return align_stages(c, "wtz_align_batch", pr, n, w, I, D, E, T, SR, out);
+	std::vector<uint64_t> h_off; CHK(batch_begin(c, h_off));
+	return align_stages(c, "wtz_align_batch", h_off, pr, n, w, I, D, E, T, SR, out);
 }
-/* the three stages of kswx_align_no_stat, shared by wtz_align_batch and wtz_alignx_batch (inside the caller's CTX_ENTER); leaves the main pool empty */
-static int align_stages(wtz_ctx *c, const char *entry, const wtz_dp_problem_t *pr, uint32_t n, int32_t w, int32_t I, int32_t D, int32_t E, int32_t T, const wtz_kextsc_t *SR, wtz_align_result_t *out){
+/* the three stages of kswx_align_no_stat, shared by wtz_align_batch and wtz_alignx_batch (behind the caller's batch_begin); leaves the main pool empty */
+static int align_stages(wtz_ctx *c, const char *entry, const std::vector<uint64_t> &h_off, const wtz_dp_problem_t *pr, uint32_t n, int32_t w, int32_t I, int32_t D, int32_t E, int32_t T, const wtz_kextsc_t *SR, wtz_align_result_t *out){
 	/* stage 1; its own checks (1 <= q_len, t_len <= 65535, the views) come before its launch, and nothing else has run by then */
 	std::vector<wtz_local_result_t> loc(n);
-	CHK(wtz_local_batch(c, pr, n, -D, -E, -I, -E, loc.data()));
+	CHK(local_run(c, h_off, pr, n, -D, -E, -I, -E, loc.data()));
 	for(uint32_t i = 0; i < n; i++){
 		wtz_align_result_t o; memset(&o, 0, sizeof o);
 		const wtz_local_result_t &l = loc[i];
@@ -286,9 +315,6 @@ static int align_stages(wtz_ctx *c, const char *entry, const wtz_dp_problem_t *p
 		out[i] = o;
 	}
 	if(T >= 0) return WTZ_OK;
-	CHK(pool_reset(c));
-	std::vector<uint64_t> h_off(c->n_reads);
-	CHK(dev_d2h(h_off.data(), c->rdoff, (size_t)c->n_reads * 8));
 	for(int side = 0; side < 2; side++){
 		std::vector<wtz_kextprob_t> hp[2]; std::vector<uint32_t> who[2];
 		for(uint32_t i = 0; i < n; i++){
@@ -328,7 +354,8 @@ static int align_stages(wtz_ctx *c, const char *entry, const wtz_dp_problem_t *p
 			}
 		}
 	}
-	return kext_leave(c, entry);
+	CHK(pool_check(c, entry));
+	return batch_leave(c);
 }
 
 #include "wtz_lib_glob.h"

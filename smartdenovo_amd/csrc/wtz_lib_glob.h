@@ -5,11 +5,9 @@
 #define WTZ_GLOB_FORM_RING 33
 #define WTZ_GLOB_FORM_SCALAR 255
 
-/* the arguments every problem of a call shares, or WTZ_E_ARG: scores as the reference's int8 matrix holds them, costs >= 0 (an opening cost of 0 is a setting like any other) */
+/* the arguments every problem of a call shares, or WTZ_E_ARG */
 static int glob_scores(const wtz_ctx *c, const char *who, int32_t o_del, int32_t e_del, int32_t o_ins, int32_t e_ins, wtz_kglobsc_t *S){
-	if(c->P.M < 1 || c->P.M > 127 || c->P.X > 0 || c->P.X < -128) return wtz_fail(WTZ_E_ARG, "%s: M must be in [1, 127] and X in [-128, 0]", who);
-	if(o_del < 0 || o_ins < 0 || e_del < 0 || e_ins < 0 || (int64_t)o_del + e_del > 32767 || (int64_t)o_ins + e_ins > 32767)
-		return wtz_fail(WTZ_E_ARG, "%s: gap costs must be >= 0 and open + extend <= 32767", who);
+	CHK(batch_scores(c, who, o_del, e_del, o_ins, e_ins, 0));
 	S->M = c->P.M; S->X = c->P.X; S->o_del = o_del; S->e_del = e_del; S->o_ins = o_ins; S->e_ins = e_ins;
 	return WTZ_OK;
 }
@@ -90,15 +88,15 @@ static __device__ void wtz_task_glob_ring(uint32_t t, const wtz_kglobprob_t *pr,
 }
 #endif
 
+template<int C> static int kglob_launch(const wtz_kglobprob_t *pr, const uint32_t *order, uint32_t n, const wtz_kglobsc_t &S, uint32_t *blk, wtz_kglobres_t *res){
 #ifdef WTZ_EMUL
-template<int C> static void kglob_emul(const wtz_kglobprob_t *pr, const uint32_t *order, uint32_t n, const wtz_kglobsc_t &S, uint32_t *blk, wtz_kglobres_t *res){
 	std::vector<uint32_t> stg(WTZ_KGLOB_STAGE_WORDS);
 	for(uint32_t b = 0; b < n; b++){ const wtz_kglobprob_t &p = pr[order[b]]; wtz_kglob_problem<C>(p, S, blk + p.tr_off, blk + p.run_off, stg.data(), res[order[b]]); }
-}
-#define KGLOB_LAUNCH(C) kglob_emul<C>(d_pr, d_order + b0, b1 - b0, S, blk, d_res)
 #else
-#define KGLOB_LAUNCH(C) WTZ_LAUNCH(wtz_kernel_kglob<C>, b1 - b0, 64, 0, g_stream, (const wtz_kglobprob_t*)d_pr, (const uint32_t*)(d_order + b0), b1 - b0, S, blk, blk, d_res)
+	WTZ_LAUNCH(wtz_kernel_kglob<C>, n, 64, 0, g_stream, pr, order, n, S, blk, blk, res);
 #endif
+	return WTZ_OK;
+}
 /* THE launch path of the banded global: the problems of one score setting.  They are ordered by form (wide forms first, then the widest K-glob instantiation)
  * and inside a form largest first, and cut into launch groups whose traces fit the main pool together; a group is one launch per form present, one wavefront
  * per problem.  hr[i], form[i]: result and form of problem i (hr[i].runs is meaningless on return); the run list of problem i is flat[pos[i], pos[i] + hr[i].n_runs).
@@ -109,75 +107,53 @@ static int glob_run(wtz_ctx *c, const char *who, std::vector<wtz_kglobprob_t> &h
 	hr.resize(n); form.resize(n); pos.assign(n, 0); flat.clear();
 	if(n == 0) return WTZ_OK;
 	const uint64_t budget = c->main_bytes > (1ull << 16) ? c->main_bytes - (1ull << 16) : 0;      /* the pool's own rounding */
-	std::vector<uint64_t> need(n); std::vector<uint32_t> order(n);
+	std::vector<uint64_t> need(n);
 	for(uint32_t i = 0; i < n; i++){
-		order[i] = i; form[i] = glob_form(hp[i]); need[i] = glob_need(hp[i], form[i], &hp[i].run_cap);
-		if(need[i] > budget){ c->last_pool_fail = 1; return wtz_fail(WTZ_E_POOL, "%s: problem %u (%d x %d, band %d) needs %llu bytes of trace in a main pool of %llu; use a larger pool",
-			who, i, hp[i].tlen, hp[i].qlen, hp[i].w, (unsigned long long)need[i], (unsigned long long)c->main_bytes); }
+		form[i] = glob_form(hp[i]); need[i] = glob_need(hp[i], form[i], &hp[i].run_cap);
+		if(need[i] > budget) return pool_fail(c, 1, "%s: problem %u (%d x %d, band %d) needs %llu bytes of trace in a main pool of %llu; use a larger pool",
+			who, i, hp[i].tlen, hp[i].qlen, hp[i].w, (unsigned long long)need[i], (unsigned long long)c->main_bytes);
 	}
-	std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b){ if(form[a] != form[b]) return form[a] > form[b]; return need[a] > need[b]; });
+	const std::vector<uint32_t> order = batch_order(n, form.data(), need);
 	for(uint32_t g0 = 0, g1; g0 < n; g0 = g1){
-		const bool wide = form[order[g0]] > 32;
+		const bool wide = form[order[g0]] > 32;      /* a wide form is a launch of its own kind: never mixed with another form */
 		uint64_t sum = 0;
 		for(g1 = g0; g1 < n && (form[order[g1]] > 32 ? form[order[g1]] == form[order[g0]] : !wide) && sum + need[order[g1]] <= budget; g1++) sum += need[order[g1]];
 		const uint32_t m = g1 - g0;
 		wtz_arena_scope launch_scope(&c->arena);      /* the buffers of this launch group go back when it ends (scopes nest) */
 		CHK(pool_reset(c));
-		std::vector<wtz_kglobprob_t> gp(m); std::vector<uint32_t> gorder(m);
+		std::vector<wtz_kglobprob_t> gp(m); std::vector<uint32_t> gorder(m), gform(m);
 		uint64_t words = 0;
 		for(uint32_t k = 0; k < m; k++){
 			wtz_kglobprob_t d = hp[order[g0 + k]];
-			if(!wide){ d.tr_off = words; words += (wtz_kglob_trace_words((int32_t)form[order[g0 + k]], d.tlen) + 63ull) & ~63ull; d.run_off = words; words += d.run_cap; }
+			gform[k] = form[order[g0 + k]];
+			if(!wide){ d.tr_off = words; words += (wtz_kglob_trace_words((int32_t)gform[k], d.tlen) + 63ull) & ~63ull; d.run_off = words; words += d.run_cap; }
 			gp[k] = d; gorder[k] = k;
 		}
 		uint32_t *blk = NULL;
-		if(!wide && pool_alloc_host(c, 0, (size_t)words * 4, (void**)&blk) != WTZ_OK){ c->last_pool_fail = 1; return wtz_fail(WTZ_E_POOL, "%s: no room for %llu bytes of trace in the main pool", who, (unsigned long long)words * 4ull); }
+		if(!wide && pool_alloc_host(c, 0, (size_t)words * 4, (void**)&blk) != WTZ_OK) return pool_fail(c, 1, "%s: no room for %llu bytes of trace in the main pool", who, (unsigned long long)words * 4ull);
 		wtz_kglobprob_t *d_pr = NULL; uint32_t *d_order = NULL; wtz_kglobres_t *d_res = NULL;
-		CHK(dev_alloc((void**)&d_pr, (size_t)m * sizeof(wtz_kglobprob_t))); CHK(dev_h2d(d_pr, gp.data(), (size_t)m * sizeof(wtz_kglobprob_t)));
-		CHK(dev_alloc((void**)&d_order, (size_t)m * 4)); CHK(dev_h2d(d_order, gorder.data(), (size_t)m * 4));
-		CHK(dev_alloc((void**)&d_res, (size_t)m * sizeof(wtz_kglobres_t))); CHK(dev_set(d_res, 0, (size_t)m * sizeof(wtz_kglobres_t)));
+		CHK(batch_upload(gp, gorder, &d_pr, &d_order, &d_res));
 		wtz_timer tm; tm.start();
 		if(wide){
 			wtz_pool_t *pool = c->dpool; const wtz_kglobprob_t *pp = d_pr;
-			if(form[order[g0]] == WTZ_GLOB_FORM_SCALAR) CHK(wtz_launch_wave<K_glob_scalar>(m, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_glob_scalar((uint32_t)t, pp, S, pool, d_res); }));
+			if(gform[0] == WTZ_GLOB_FORM_SCALAR) CHK(wtz_launch_wave<K_glob_scalar>(m, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_glob_scalar((uint32_t)t, pp, S, pool, d_res); }));
 #ifndef WTZ_EMUL
 			else CHK(wtz_launch_coop<K_glob_ring>(m, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_glob_ring((uint32_t)t, pp, S, pool, d_res); }, WTZ_GAP_WIDE_LDS_BYTES));
 #endif
-		} else for(uint32_t b0 = 0, b1; b0 < m; b0 = b1){
-			const uint32_t C = form[order[g0 + b0]];
-			for(b1 = b0 + 1; b1 < m && form[order[g0 + b1]] == C; b1++){}
-			switch(C){
-				case 1: KGLOB_LAUNCH(1); break;
-				case 2: KGLOB_LAUNCH(2); break;
-				case 4: KGLOB_LAUNCH(4); break;
-				case 8: KGLOB_LAUNCH(8); break;
-				case 16: KGLOB_LAUNCH(16); break;
-				default: KGLOB_LAUNCH(32); break;
-			}
-		}
-		CHK(dev_sync());
-		c->cnt.ms_kglob += tm.stop();
-		std::vector<wtz_kglobres_t> gr(m);
-		CHK(dev_d2h(gr.data(), d_res, (size_t)m * sizeof(wtz_kglobres_t)));
+		} else CHK(for_each_form(m, [&](uint32_t b){ return gform[b]; }, [&](auto K, uint32_t b0, uint32_t b1){ return kglob_launch<decltype(K)::value>(d_pr, d_order + b0, b1 - b0, S, blk, d_res); }));
+		std::vector<wtz_kglobres_t> gr;
+		CHK(batch_fetch(tm, c->cnt.ms_kglob, m, d_res, gr));
 		CHK(pool_check(c, who));
 		/* the run lists of the group, packed on the device, behind those of the groups before */
-		std::vector<uint64_t> off((size_t)m + 1); uint64_t tot = 0;
+		std::vector<uint64_t> off((size_t)m + 1, 0);
 		for(uint32_t k = 0; k < m; k++){
-			if(gr[k].bad){ c->last_pool_fail = 1; return wtz_fail(WTZ_E_POOL, "%s: problem %u ran out of scratch", who, order[g0 + k]); }
-			off[k] = tot; tot += gr[k].n_runs;
+			if(gr[k].bad) return pool_fail(c, 1, "%s: problem %u ran out of scratch", who, order[g0 + k]);
+			off[k + 1] = off[k] + gr[k].n_runs;
 		}
-		off[m] = tot;
 		const size_t at = flat.size();
-		if(tot){
-			uint64_t *d_off = NULL; uint32_t *d_flat = NULL;
-			CHK(dev_alloc((void**)&d_off, ((size_t)m + 1) * 8)); CHK(dev_h2d(d_off, off.data(), ((size_t)m + 1) * 8));
-			CHK(dev_alloc((void**)&d_flat, (size_t)tot * 4));
-			const wtz_kglobres_t *rs = d_res;
-			CHK(wtz_launch<K_globcopy>(m, [=] WTZ_LAMBDA (uint64_t t){ const uint64_t o = d_off[t], e = d_off[t + 1]; const uint32_t *src = rs[t].runs; for(uint64_t k = o; k < e; k++) d_flat[k] = src[k - o]; }));
-			CHK(dev_sync());
-			flat.resize(at + (size_t)tot);
-			CHK(dev_d2h(flat.data() + at, d_flat, (size_t)tot * 4));
-		}
+		flat.resize(at + (size_t)off[m]);
+		const wtz_kglobres_t *rs = d_res;
+		CHK(pack_runs<K_globcopy>(off, [=] WTZ_LAMBDA (uint64_t t) -> const uint32_t* { return rs[t].runs; }, flat.data() + at));
 		for(uint32_t k = 0; k < m; k++){
 			const uint32_t i = order[g0 + k];
 			hr[i] = gr[k]; hr[i].runs = NULL; pos[i] = at + off[k];
@@ -191,11 +167,8 @@ static int glob_run(wtz_ctx *c, const char *who, std::vector<wtz_kglobprob_t> &h
 		}
 		c->cnt.n_kglob += m;
 	}
-	CHK(pool_reset(c));
-	c->main_used_call = 0;
-	return WTZ_OK;
+	return batch_leave(c);
 }
-#undef KGLOB_LAUNCH
 
 /* the fold of kswx.h:1468-1477 over a run list: op 1 (query only) counts as del, op 2 (target only) as ins - the convention of kswx_gen_cigar_core2, not the one
  * of the gap task's fold behind wtz_test_dp */
@@ -203,36 +176,37 @@ static void glob_fold_kswx(const uint32_t *a, uint32_t n, int32_t *aln, int32_t 
 	*aln = *ins = *del = 0;
 	for(uint32_t k = 0; k < n; k++){ const uint32_t op = a[k] & 0xFu; const int32_t len = (int32_t)(a[k] >> 4); *aln += len; if(op == 1) *del += len; else if(op == 2) *ins += len; }
 }
+/* the CIGARs of a glob_run to the caller: result_of(k) is where problem k's result goes (it fills what is its own and returns it); aln / ins / del are folded from
+ * the run list and, where the caller gave a buffer, the lists are laid one behind the other into it */
+template<typename F> static int glob_hand_out(const char *who, const std::vector<wtz_kglobres_t> &hr, const std::vector<uint32_t> &flat, const std::vector<uint64_t> &pos,
+		uint32_t *cigar, uint64_t cigar_cap, F result_of){
+	uint64_t tot = 0, at = 0;
+	for(size_t k = 0; k < hr.size(); k++) tot += hr[k].n_runs;
+	if(cigar && tot > cigar_cap) return wtz_fail(WTZ_E_ARG, "%s: CIGAR buffer too small (%llu words needed)", who, (unsigned long long)tot);
+	for(size_t k = 0; k < hr.size(); k++){
+		auto &o = result_of(k);
+		glob_fold_kswx(flat.data() + pos[k], hr[k].n_runs, &o.aln, &o.ins, &o.del);
+		if(cigar){ o.cigar_off = at; o.cigar_len = hr[k].n_runs; if(hr[k].n_runs) memcpy(cigar + at, flat.data() + pos[k], (size_t)hr[k].n_runs * 4); at += hr[k].n_runs; }
+	}
+	return WTZ_OK;
+}
 
 /* ksw_global2 (ksw.c:503-586) for n independent problems on views of the uploaded reads */
 extern "C" int wtz_global_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32_t n, int32_t o_del, int32_t e_del, int32_t o_ins, int32_t e_ins,
 		wtz_global_result_t *out, uint32_t *cigar, uint64_t cigar_cap){
-	if(!c || !c->bits) return wtz_fail(WTZ_E_ARG, "reads not uploaded");
-	if(n == 0) return WTZ_OK;
-	if(!pr || !out || (!cigar && cigar_cap)) return wtz_fail(WTZ_E_ARG, "null argument");
-	if(n > 0x7FFFFFFFu) return wtz_fail(WTZ_E_ARG, "wtz_global_batch: more than 2^31 - 1 problems in one call");
+	BATCH_ARGS(c, n, pr && out && (cigar || !cigar_cap), "wtz_global_batch", "problems");
 	wtz_kglobsc_t S; CHK(glob_scores(c, "wtz_global_batch", o_del, e_del, o_ins, e_ins, &S));
 	CTX_ENTER(c);
-	CHK(pool_reset(c));
-	std::vector<uint64_t> h_off(c->n_reads);
-	CHK(dev_d2h(h_off.data(), c->rdoff, (size_t)c->n_reads * 8));
+	std::vector<uint64_t> h_off; CHK(batch_begin(c, h_off));
 	std::vector<wtz_kglobprob_t> hp(n);
 	for(uint32_t i = 0; i < n; i++) CHK(glob_plan(c, h_off, pr[i], i, S, &hp[i]));
 	std::vector<wtz_kglobres_t> hr; std::vector<uint32_t> form, flat; std::vector<uint64_t> pos;
 	CHK(glob_run(c, "wtz_global_batch", hp, S, hr, form, flat, pos));
-	uint64_t tot = 0;
-	for(uint32_t i = 0; i < n; i++) tot += hr[i].n_runs;
-	if(cigar && tot > cigar_cap) return wtz_fail(WTZ_E_ARG, "wtz_global_batch: CIGAR buffer too small (%llu words needed)", (unsigned long long)tot);
-	uint64_t at = 0;
-	for(uint32_t i = 0; i < n; i++){
-		wtz_global_result_t o; memset(&o, 0, sizeof o);
-		o.score = hr[i].score; o.mat = hr[i].mat; o.mis = hr[i].mis;
-		glob_fold_kswx(flat.data() + pos[i], hr[i].n_runs, &o.aln, &o.ins, &o.del);
-		o.form_used = form[i]; o.cells = hr[i].cells;
-		if(cigar){ o.cigar_off = at; o.cigar_len = hr[i].n_runs; if(hr[i].n_runs) memcpy(cigar + at, flat.data() + pos[i], (size_t)hr[i].n_runs * 4); at += hr[i].n_runs; }
-		out[i] = o;
-	}
-	return WTZ_OK;
+	return glob_hand_out("wtz_global_batch", hr, flat, pos, cigar, cigar_cap, [&](size_t i) -> wtz_global_result_t& {
+		wtz_global_result_t &o = out[i]; memset(&o, 0, sizeof o);
+		o.score = hr[i].score; o.mat = hr[i].mat; o.mis = hr[i].mis; o.form_used = form[i]; o.cells = hr[i].cells;
+		return o;
+	});
 }
 
 /* the band of kswx_gen_cigar_core2 (kswx.h:1452-1461) for the rectangle [tb, te) x [qb, qe) of score `score`: double arithmetic truncated to int where the reference
@@ -258,12 +232,11 @@ extern "C" int wtz_alignx_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32
 	if(n == 0) return WTZ_OK;
 	if(!cigar && cigar_cap) return wtz_fail(WTZ_E_ARG, "null argument");
 	wtz_kglobsc_t S; CHK(glob_scores(c, "wtz_alignx_batch", -D, -E, -I, -E, &S));
+	CHK(batch_count(n, "wtz_local_batch", "problems"));      /* stage 1's limit, under its name */
 	CTX_ENTER(c);
+	std::vector<uint64_t> h_off; CHK(batch_begin(c, h_off));
 	std::vector<wtz_align_result_t> ar(n);
-	CHK(align_stages(c, "wtz_alignx_batch", pr, n, w < 0 ? 0 : w, I, D, E, T, SR, ar.data()));
-	CHK(pool_reset(c));
-	std::vector<uint64_t> h_off(c->n_reads);
-	CHK(dev_d2h(h_off.data(), c->rdoff, (size_t)c->n_reads * 8));
+	CHK(align_stages(c, "wtz_alignx_batch", h_off, pr, n, w < 0 ? 0 : w, I, D, E, T, SR, ar.data()));
 	std::vector<wtz_kglobprob_t> hp; std::vector<uint32_t> who;
 	for(uint32_t i = 0; i < n; i++){
 		wtz_alignx_result_t o; memset(&o, 0, sizeof o);
@@ -284,15 +257,9 @@ extern "C" int wtz_alignx_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, uint32
 	}
 	std::vector<wtz_kglobres_t> hr; std::vector<uint32_t> form, flat; std::vector<uint64_t> pos;
 	CHK(glob_run(c, "wtz_alignx_batch", hp, S, hr, form, flat, pos));
-	uint64_t tot = 0;
-	for(size_t k = 0; k < hr.size(); k++) tot += hr[k].n_runs;
-	if(cigar && tot > cigar_cap) return wtz_fail(WTZ_E_ARG, "wtz_alignx_batch: CIGAR buffer too small (%llu words needed)", (unsigned long long)tot);
-	uint64_t at = 0;
-	for(size_t k = 0; k < hr.size(); k++){
+	return glob_hand_out("wtz_alignx_batch", hr, flat, pos, cigar, cigar_cap, [&](size_t k) -> wtz_alignx_result_t& {
 		wtz_alignx_result_t &o = out[who[k]];
 		o.score = hr[k].score; o.mat = hr[k].mat; o.mis = hr[k].mis; o.form_used = form[k];
-		glob_fold_kswx(flat.data() + pos[k], hr[k].n_runs, &o.aln, &o.ins, &o.del);
-		if(cigar){ o.cigar_off = at; o.cigar_len = hr[k].n_runs; if(hr[k].n_runs) memcpy(cigar + at, flat.data() + pos[k], (size_t)hr[k].n_runs * 4); at += hr[k].n_runs; }
-	}
-	return WTZ_OK;
+		return o;
+	});
 }

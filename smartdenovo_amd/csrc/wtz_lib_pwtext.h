@@ -32,15 +32,10 @@ static int pwt_plan(const wtz_ctx *c, const std::vector<uint64_t> &h_off, const 
 /* kswx_cigar2pairwise (kswx.h:1150-1194) + the marker line of pairaln.c:115-125 for n alignments on views of the uploaded reads */
 extern "C" int wtz_pwtext_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, const wtz_pwtext_in_t *in, uint32_t n, const uint32_t *cigar, uint64_t n_ops,
 		wtz_pwtext_result_t *out, char *text, uint64_t text_cap){
-	if(!c || !c->bits) return wtz_fail(WTZ_E_ARG, "reads not uploaded");
-	if(n == 0) return WTZ_OK;
-	if(!pr || !in || !out || (!cigar && n_ops) || (!text && text_cap)) return wtz_fail(WTZ_E_ARG, "null argument");
-	if(n > 0x7FFFFFFFu) return wtz_fail(WTZ_E_ARG, "wtz_pwtext_batch: more than 2^31 - 1 alignments in one call");
+	BATCH_ARGS(c, n, pr && in && out && (cigar || !n_ops) && (text || !text_cap), "wtz_pwtext_batch", "alignments");
 	CTX_ENTER(c);
-	CHK(pool_reset(c));
+	std::vector<uint64_t> h_off; CHK(batch_begin(c, h_off));
 	c->main_used_call = 0;
-	std::vector<uint64_t> h_off(c->n_reads);
-	CHK(dev_d2h(h_off.data(), c->rdoff, (size_t)c->n_reads * 8));
 	std::vector<pwt_plan_t> plan(n);
 	std::vector<uint64_t> toff((size_t)n + 1);
 	uint64_t tot = 0;
@@ -50,8 +45,8 @@ extern "C" int wtz_pwtext_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, const 
 	const uint64_t slack = 4096, budget = c->main_bytes > (1ull << 16) + slack ? c->main_bytes - (1ull << 16) - slack : 0;      /* the pool's own rounding, the blocks' alignment */
 	for(uint32_t i = 0; i < n; i++){
 		wtz_pwtext_result_t o; memset(&o, 0, sizeof o); o.text_off = toff[i]; o.cols = plan[i].d.cols; out[i] = o;
-		if(text && plan[i].need > budget){ c->last_pool_fail = 1; return wtz_fail(WTZ_E_POOL, "wtz_pwtext_batch: alignment %u (%u operations, %u columns) needs %llu bytes in a main pool of %llu; use a larger pool",
-			i, plan[i].d.n_ops, plan[i].d.cols, (unsigned long long)plan[i].need, (unsigned long long)c->main_bytes); }
+		if(text && plan[i].need > budget) return pool_fail(c, 1, "wtz_pwtext_batch: alignment %u (%u operations, %u columns) needs %llu bytes in a main pool of %llu; use a larger pool",
+			i, plan[i].d.n_ops, plan[i].d.cols, (unsigned long long)plan[i].need, (unsigned long long)c->main_bytes);
 	}
 	if(!text) return WTZ_OK;      /* the sizing call */
 	for(uint32_t g0 = 0, g1; g0 < n; g0 = g1){
@@ -75,7 +70,7 @@ extern "C" int wtz_pwtext_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, const 
 		/* one block of the main pool: the table, the CIGAR words, the picture */
 		const uint64_t tab_bytes = (8ull * ops + 255ull) & ~255ull, cig_bytes = (4ull * ops + 255ull) & ~255ull;
 		uint8_t *blk = NULL;
-		if(pool_alloc_host(c, 0, (size_t)(tab_bytes + cig_bytes + tbytes + 256ull), (void**)&blk) != WTZ_OK){ c->last_pool_fail = 1; return wtz_fail(WTZ_E_POOL, "wtz_pwtext_batch: no room for %llu bytes in the main pool", (unsigned long long)(tab_bytes + cig_bytes + tbytes)); }
+		if(pool_alloc_host(c, 0, (size_t)(tab_bytes + cig_bytes + tbytes + 256ull), (void**)&blk) != WTZ_OK) return pool_fail(c, 1, "wtz_pwtext_batch: no room for %llu bytes in the main pool", (unsigned long long)(tab_bytes + cig_bytes + tbytes));
 		unsigned long long *d_tab = (unsigned long long*)blk; uint32_t *d_cig = (uint32_t*)(blk + tab_bytes); char *d_text = (char*)(blk + tab_bytes + cig_bytes);
 		wtz_pwtprob_t *d_pr = NULL; wtz_pwttile_t *d_tiles = NULL; uint32_t *d_nent = NULL;
 		CHK(dev_alloc((void**)&d_pr, (size_t)m * sizeof(wtz_pwtprob_t))); CHK(dev_h2d(d_pr, gp.data(), (size_t)m * sizeof(wtz_pwtprob_t)));
@@ -99,7 +94,5 @@ extern "C" int wtz_pwtext_batch(wtz_ctx_t *c, const wtz_dp_problem_t *pr, const 
 		CHK(pool_check(c, "wtz_pwtext_batch"));
 		c->cnt.n_pwtext += m; c->cnt.bytes_pwtext += tbytes;
 	}
-	CHK(pool_reset(c));
-	c->main_used_call = 0;
-	return WTZ_OK;
+	return batch_leave(c);
 }

@@ -135,18 +135,14 @@ static __device__ void wtz_task_test_global(uint32_t t, const wtz_dpprob_dev_t *
 #endif
 
 extern "C" int wtz_test_dp(wtz_ctx_t *c, int32_t kind, int32_t form, const wtz_dp_problem_t *pr, uint32_t n, wtz_dp_result_t *out, uint32_t *cigar, uint64_t cigar_cap){
-	if(!c || !c->bits) return wtz_fail(WTZ_E_ARG, "reads not uploaded");
-	if(n == 0) return WTZ_OK;
-	if(!pr || !out || (!cigar && cigar_cap)) return wtz_fail(WTZ_E_ARG, "null argument");
+	BATCH_ARGS(c, n, pr && out && (cigar || !cigar_cap), NULL, NULL);
 #ifdef WTZ_EMUL
 	(void)kind; (void)form;
 	return wtz_fail(WTZ_E_STATE, "wtz_test_dp drives the DEVICE forms of the banded DPs: it needs the HIP build");
 #else
 	CTX_ENTER(c);
-	CHK(pool_reset(c));
+	std::vector<uint64_t> h_off; CHK(batch_begin(c, h_off));
 	std::vector<wtz_dpprob_dev_t> hp(n);
-	std::vector<uint64_t> h_off(c->n_reads);
-	CHK(dev_d2h(h_off.data(), c->rdoff, (size_t)c->n_reads * 8));
 	for(uint32_t i = 0; i < n; i++){
 		const wtz_dp_problem_t &p = pr[i];
 		wtz_dpprob_dev_t d; CHK(dp_problem_views(c, h_off, p, i, true, 0, &d.q, &d.t)); d.qlen = p.q_len; d.tlen = p.t_len; d.init_score = p.init_score; d.W = p.W;
@@ -179,8 +175,7 @@ extern "C" int wtz_test_dp(wtz_ctx_t *c, int32_t kind, int32_t form, const wtz_d
 		}
 	} else if(kind == WTZ_DP_FIXED || kind == WTZ_DP_GLOBAL){
 		wtz_dpprob_dev_t *d_pr = NULL; wtz_dpres_dev_t *d_res = NULL;
-		CHK(dev_alloc((void**)&d_pr, (size_t)n * sizeof(wtz_dpprob_dev_t))); CHK(dev_h2d(d_pr, hp.data(), (size_t)n * sizeof(wtz_dpprob_dev_t)));
-		CHK(dev_alloc((void**)&d_res, (size_t)n * sizeof(wtz_dpres_dev_t))); CHK(dev_set(d_res, 0, (size_t)n * sizeof(wtz_dpres_dev_t)));
+		CHK(batch_upload(hp, std::vector<uint32_t>(), &d_pr, (uint32_t**)NULL, &d_res));
 		const wtz_params_t *dP = c->dP; wtz_pool_t *pool = c->dpool;
 		if(kind == WTZ_DP_FIXED && form == 64){
 			CHK(wtz_launch_coop<K_test_lane>(n, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_test_lane((uint32_t)t, d_pr, dP, pool, d_res); }, 0));

@@ -35,3 +35,13 @@ def test_runs_that_end_early(exe):
     assert got["rc"] == 1 and "-W 2000" in got["err"] and got["out"] == b""
     got = pairalnsets.run(exe, EXTRA, ["pairaln_empty.fa.gz"], ["-a"])
     assert got["rc"] == 0 and got["out"].decode() == MAN["empty_record"]["stdout"]
+
+
+def test_a_pool_too_small_for_one_pair_ends_the_run(exe):
+    """--pool-mb 1 (tests/test_halving.py): the file is one pair, so the first call is the call of one item and the run ends there, without a halving; the
+    fixtures have no pool at which a call fails and its halves succeed"""
+    got = pairalnsets.run(exe, ["--gpu", "0", "--pool-mb", "1"], ["pairaln_long.fa.gz"], ["-a"])
+    assert got["rc"] == 1 and "scratch pool too small even for one pair: " in got["err"] and got["err"].endswith(" (use --pool-gb) --\n")
+    assert got["out"] == b""
+    got = pairalnsets.run(exe, ["--gpu", "0", "--pool-mb", "1"], ["pairaln_pairs.fa.gz"], ["-a"])
+    assert got["rc"] == 0 and got["out"].decode() == MAN["cases"]["a"]["stdout"]

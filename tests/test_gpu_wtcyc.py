@@ -37,3 +37,10 @@ def test_runs_that_end_early(exe, tmp_path):
     r = subprocess.run([exe] + EXTRA + ["-o", str(keep), os.path.join(cycsets.GOLDEN, "cyc_wrapped.fa.gz")], capture_output=True, text=True)
     assert r.returncode == 1 and r.stderr.startswith("File exists! '%s'\n\n" % keep) and keep.read_text() == "mine\n"
     assert MAN["cases"]["wrapped"]["o_lines"] == 3
+
+
+def test_a_pool_too_small_for_one_read_ends_the_run(exe, tmp_path):
+    """--pool-mb 1 (tests/test_halving.py): the call is halved down to one read and the run ends; the fixture has no pool at which halves succeed"""
+    got = cycsets.run(exe, ["--gpu", "0", "--pool-mb", "1"], os.path.join(cycsets.GOLDEN, "cyc_reads.fa.gz"), ["-o", "{o}", "-a", "{a}"], str(tmp_path))
+    assert got["rc"] == 1 and "scratch pool too small even for one read: " in got["err"] and got["err"].endswith(" (use --pool-gb) --\n")
+    assert got["a"] == b"" and got["o"] == b""

@@ -8,6 +8,7 @@ import subprocess
 import pytest
 
 import cycsets
+import emultools
 
 ROOT = cycsets.ROOT
 MAN = json.load(open(os.path.join(cycsets.GOLDEN, "cyc_manifest.json")))
@@ -17,15 +18,7 @@ EXTRA = ["--pool-gb", "1"]
 @pytest.fixture(scope="module")
 def exe():
     """wtcyc_emul: the same main against the libwtz_emul.so that tests/emul/build_emul.sh produces"""
-    emul = os.path.join(ROOT, "tests", "emul")
-    subprocess.run([os.path.join(emul, "build_emul.sh")], check=True)
-    out = os.path.join(emul, "wtcyc_emul")
-    src = os.path.join(ROOT, "smartdenovo_amd", "csrc", "host", "wtcyc_main.c")
-    deps = [src, os.path.join(emul, "libwtz_emul.so"), os.path.join(ROOT, "smartdenovo_amd", "csrc", "host", "wtz_host.h"), os.path.join(ROOT, "include", "wtzmo_hip.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        subprocess.run(["gcc", "-std=gnu11", "-O2", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Wno-unused-parameter", "-Wno-sign-compare", "-Wno-unused-function",
-                        "-I" + os.path.join(ROOT, "include"), "-o", out, src, "-L" + emul, "-lwtz_emul", "-Wl,-rpath,$ORIGIN", "-lstdc++", "-lm", "-lpthread"], check=True)
-    return out
+    return emultools.build("wtcyc")
 
 
 def check_case(exe, extra, name, workdir):

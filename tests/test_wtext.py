@@ -45,15 +45,20 @@ def overlap_inputs(zmo_exe, tmp_factory, tag):
     return _made[key]
 
 
-def run_ext(exe, name, files, tmp, extra=()):
+def ext_cmd(exe, name, files, out, extra=()):
+    """one run of a golden case into `out`: the finished process"""
     case = MAN["cases"][name]
-    out = os.path.join(str(tmp), "x.ovl")
     js = []
     for o in case["ovls"]:
         js += ["-j", files[o]]
-    cmd = [exe, "-t", "1", "-i", files["fa"]] + js + ["-fo", out] + _at(case["argv"]) + list(extra)
-    r = subprocess.run(cmd, capture_output=True)
-    assert r.returncode == 0, "%s failed (%d): %s" % (" ".join(cmd), r.returncode, r.stderr.decode()[-2000:])
+    return subprocess.run([exe, "-t", "1", "-i", files["fa"]] + js + ["-fo", out] + _at(case["argv"]) + list(extra), capture_output=True)
+
+
+def run_ext(exe, name, files, tmp, extra=()):
+    case = MAN["cases"][name]
+    out = os.path.join(str(tmp), "x.ovl")
+    r = ext_cmd(exe, name, files, out, extra)
+    assert r.returncode == 0, "%s failed (%d): %s" % (" ".join(r.args), r.returncode, r.stderr.decode()[-2000:])
     full = open(out, "rb").read()
     if md5_file(out) != case["md5_full"]:       # say where
         want = gzip.open(os.path.join(GOLD, "ext_%s.ovl16.gz" % name)).read().split(b"\n")
