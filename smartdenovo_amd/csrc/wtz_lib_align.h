@@ -52,7 +52,7 @@ static int run_stitch_fused(wtz_ctx *c, const wtz_env_t &V, const wtz_alnitem_t 
 			nb += wtz_ext_trace_need(d_rgeo[2 * t], d_rgeo[2 * t + 1], 0, pW, pM, pO, pE, pT, &qb, (int32_t*)NULL);
 			const uint32_t rows = (uint32_t)qa + (uint32_t)qb;
 			/* which form takes the item (bit 32 of the key: the items of the 32-bit form end up behind those of the packed form, both longest-first): the packed
-			 * form needs both extensions inside its 16-bit window - the left one's init_score is known, the right one's is not (wtz_pk_window_any_init) */
+			 * form needs both extensions inside its 16-bit window - the left one's init_score is known, the right one's is not (wtz_pk_window_range) */
 			uint32_t to_fr = 0;
 			if(use_pk){
 				if(j.valid && j.qlen > 0 && j.tlen > 0){

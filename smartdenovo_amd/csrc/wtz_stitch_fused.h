@@ -24,7 +24,7 @@
 template<int TW>
 __device__ __attribute__((noinline)) bool wtz_extjob_run_fr_call(wtz_extjob_t *job, const wtz_params_t *Pm, wtz_pool_t *pool, wtz_pool_t *tpool){
 	__shared__ uint64_t stb[TW];      /* declared here, not passed in: the row loop reads it with LDS instructions, not through a generic pointer */
-	return wtz_extjob_run_fr<TW, 0, 32>(job, Pm, pool, tpool, stb);
+	return wtz_extjob_run_fr<TW>(job, Pm, pool, tpool, stb);
 }
 template<int TW>
 __device__ __attribute__((noinline)) void wtz_stitch_mid_call(uint32_t t, const wtz_env_t *V, const wtz_alnitem_t *items, wtz_stitch_state_t *sts, const wtz_extjob_t *jobsL, wtz_extjob_t *jobsR, const wtz_gapres_t *gaps){

@@ -20,12 +20,11 @@
  *   - the row maximum: lanes entirely beyond the band end are masked after their local reduction; the one lane the band end cuts
  *     through checks whether its local arg-max fell on a cell beyond it and only then (rare: that cell is W columns off the running
  *     maximum) the wave repeats the reduction with per-cell masks.
- * Trace layout (this file owns it; wtz_sw_frame16.h re-stages its nibbles into it, wtz_shift_traceback in wtz_sw_wave.h walks it): rows are carved from the
- * transient pool 64 at a time (chunk table tr.chunk, one pointer per 64 rows); a row is zrow = ceil(C/4) * 256 bytes in the lane-transposed order
- * (row, k/4, lane, k%4), so that each of the ceil(C/4) stores of a row writes 256 contiguous bytes; byte k of lane l belongs to band-relative column l*C + k
- * and holds the four decisions only (bit 3 m<e, bit 2 max(m,e)<f, bit 1 E extended, bit 0 F extended); only lanes that own band cells store, what lies right
- * of the band end is never read by the walk.  The band start of row i goes to zb[i].  The "bases equal" bit of the older form (two ops per cell to insert) is
- * gone: the walk counts diagonal steps and gap runs, and matches / mismatches follow from the score (see wtz_shift_traceback<C, NL, false>).
+ * Trace layout (this file owns it, both frame forms write it; wtz_shift_traceback in wtz_sw_wave.h walks it and describes the cell):
+ * rows are carved from the transient pool 64 at a time (chunk table tr.chunk, one pointer per 64 rows); a row is zrow = CQ * 256 bytes (CQ = the form's
+ * trace dwords per lane: ceil(C/4) here, ceil(C2/4) in wtz_sw_frame16.h) in the lane-transposed order (row, q, lane), so that each of the CQ stores of a row writes 256 contiguous bytes;
+ * byte k of lane l belongs to band-relative column l*C + k; only lanes that own band cells store, what lies right of the band end is never read by the walk.
+ * The band start of row i goes to zb[i].
  * The once-per-64-rows block of the row loop (next trace chunk, next query words): every branch of it is wave-uniform BY CONSTRUCTION (readfirstlane) and it
  * ends in an explicit vmcnt(0).  The wait-count pass works on the structurised CFG, and one vector load it believes may still be in flight when the row body
  * starts makes every row wait for vmcnt(0) - i.e. for the previous row's trace stores, the latency this kernel hides.  For the same reason there is a vmcnt(0)
@@ -43,15 +42,6 @@
 #ifndef WTZ_OCC_EXTFR
 #define WTZ_OCC_EXTFR 2
 #endif
-/* resident waves per SIMD the band classes of the split launch are compiled for (WTZ_EXT_FR_SPLIT=1: bands of <= 16 / <= 28 / <= 32 columns per lane in three
- * concurrent launches, each kernel with the register budget of its widest row body) */
-#ifndef WTZ_OCC_EXTFR_LO
-#define WTZ_OCC_EXTFR_LO 4
-#endif
-#ifndef WTZ_OCC_EXTFR_MID
-#define WTZ_OCC_EXTFR_MID 2
-#endif
-#define WTZ_FR_OCC(CHI) ((CHI) <= 16 ? WTZ_OCC_EXTFR_LO : ((CHI) <= 28 ? WTZ_OCC_EXTFR_MID : WTZ_OCC_EXTFR))
 
 /* pins a value in program order: the trace bytes must be computed where the cell is, not sunk into the conditional store block */
 #define WTZ_PIN(v) asm volatile("" : "+v"(v))
@@ -128,15 +118,11 @@ WTZ_D void wtz_fr_row(int32_t (&hv)[C], int32_t (&ev)[C], uint32_t (&zw)[(C + 3)
 		const int32_t en = e > t ? e : t;
 		d = __builtin_amdgcn_alignbit(d, (uint32_t)(t - f), 31);                /* F extended */
 		f = f > t ? f : t;
-		hv[k] = h; ev[k] = en;                                                   /* no "bases equal" bit in this form's trace byte: mat / mis follow from the score (wtz_shift_traceback<.., false>) */
+		hv[k] = h; ev[k] = en;                                                   /* no "bases equal" bit in this form's trace byte: mat / mis follow from the score (wtz_shift_traceback) */
 		const int32_t kk = (int32_t)(((uint32_t)h << 11) + (uint32_t)ck[k]);
 		key = kk > key ? kk : key;
 		zw[k >> 2] |= d << (8 * (k & 3));
-		if constexpr((k & 3) == 3 || k == C - 1){ WTZ_PIN(zw[k >> 2]);
-#ifdef WTZ_FR_SCHED_BARRIER
-			__builtin_amdgcn_sched_barrier(0);
-#endif
-		}
+		if constexpr((k & 3) == 3 || k == C - 1){ WTZ_PIN(zw[k >> 2]); }
 	});
 	lkey = key;
 }
@@ -336,13 +322,13 @@ WTZ_D wtz_aln_t wtz_extend_shift_fr(int32_t qlen, const wtz_seq_packed &query, i
 	else { x.score = mx; x.qe = mi; x.te = mj; }
 	__threadfence_block();
 	const wtz_tb_score sc = { M, X, O, E, init_score };
-	if(!wtz_shift_traceback<C, 64, false>(x, zchunk, zb, zrow, tb, cigars, &sc)) *ok = false, *consistent = false;
+	if(!wtz_shift_traceback<C, 64>(x, zchunk, zb, zrow, tb, cigars, &sc)) *ok = false, *consistent = false;
 	return wtz_bcast_aln(x);
 }
 
 /* one K-sw3 job on the calling wavefront in the frame form; false = the job is outside the envelope (or its counts did not follow from the score) and stays
  * open for the general kernel (wtz_kernel_extjobs).  stb: TW 64-bit words of LDS of this wave. */
-template<int TW, int CLO, int CHI>
+template<int TW>
 WTZ_D bool wtz_extjob_run_fr(wtz_extjob_t *job, const wtz_params_t *Pm, wtz_pool_t *pool, wtz_pool_t *tpool, uint64_t *stb){
 	if(!job->valid || job->done) return true;
 	const int lane = (int)(threadIdx.x & 63);
@@ -359,7 +345,6 @@ WTZ_D bool wtz_extjob_run_fr(wtz_extjob_t *job, const wtz_params_t *Pm, wtz_pool
 		if((long long)init_score + (long long)(Pm->M > 0 ? Pm->M : -Pm->M) * (ql < tl ? ql : tl) + span * aE + 10000 + aX + aO + 16 >= (1 << 20)) return false;
 		if(aE > 255 || Pm->M == Pm->X) return false;
 	}
-	if(Cw <= CLO || (CHI < 32 && Cw > CHI)) return false;
 	wtz_trace_t tr; tr.chunk = NULL; tr.zb = NULL; tr.n_chunk = 0; tr.zrow = 0; tr.cap_rows = 0;
 	wtz_cigar_t cg; cg.a = NULL; cg.n = cg.cap = 0; cg.pool = pool; cg.bad = 0;
 	if(lane == 0) cg.init(pool, (uint32_t)ql / 2u + 16u);
@@ -367,20 +352,20 @@ WTZ_D bool wtz_extjob_run_fr(wtz_extjob_t *job, const wtz_params_t *Pm, wtz_pool
 	wtz_aln_t x;
 #define WTZ_EXTFR_CASE(CM) x = wtz_extend_shift_fr<CM>(job->qlen, job->q, job->tlen, job->t, job->init_score, ql, tl, W, Pm->M, Pm->X, Pm->O, Pm->E, Pm->T, stb, tr, tpool, cg, &cells, &ok, &consistent)
 	/* one instantiation per two columns per lane from 4 on (round 6: steps of four left the mean job a sixth of its cells beyond its band's widest row) */
-	if(Cw <= 4){ if(CLO < 4 && CHI >= 4) WTZ_EXTFR_CASE(4); }
-	else if(Cw <= 6){ if(CLO < 6 && CHI >= 6) WTZ_EXTFR_CASE(6); }
-	else if(Cw <= 8){ if(CLO < 8 && CHI >= 8) WTZ_EXTFR_CASE(8); }
-	else if(Cw <= 10){ if(CLO < 10 && CHI >= 10) WTZ_EXTFR_CASE(10); }
-	else if(Cw <= 12){ if(CLO < 12 && CHI >= 12) WTZ_EXTFR_CASE(12); }
-	else if(Cw <= 14){ if(CLO < 14 && CHI >= 14) WTZ_EXTFR_CASE(14); }
-	else if(Cw <= 16){ if(CLO < 16 && CHI >= 16) WTZ_EXTFR_CASE(16); }
-	else if(Cw <= 18){ if(CLO < 18 && CHI >= 18) WTZ_EXTFR_CASE(18); }
-	else if(Cw <= 20){ if(CLO < 20 && CHI >= 20) WTZ_EXTFR_CASE(20); }
-	else if(Cw <= 22){ if(CLO < 22 && CHI >= 22) WTZ_EXTFR_CASE(22); }
-	else if(Cw <= 24){ if(CLO < 24 && CHI >= 24) WTZ_EXTFR_CASE(24); }
-	else if(Cw <= 26){ if(CLO < 26 && CHI >= 26) WTZ_EXTFR_CASE(26); }
-	else if(Cw <= 28){ if(CLO < 28 && CHI >= 28) WTZ_EXTFR_CASE(28); }
-	else { if(CHI >= 32) WTZ_EXTFR_CASE(32); }
+	if(Cw <= 4)WTZ_EXTFR_CASE(4);
+	else if(Cw <= 6)WTZ_EXTFR_CASE(6);
+	else if(Cw <= 8)WTZ_EXTFR_CASE(8);
+	else if(Cw <= 10)WTZ_EXTFR_CASE(10);
+	else if(Cw <= 12)WTZ_EXTFR_CASE(12);
+	else if(Cw <= 14)WTZ_EXTFR_CASE(14);
+	else if(Cw <= 16)WTZ_EXTFR_CASE(16);
+	else if(Cw <= 18)WTZ_EXTFR_CASE(18);
+	else if(Cw <= 20)WTZ_EXTFR_CASE(20);
+	else if(Cw <= 22)WTZ_EXTFR_CASE(22);
+	else if(Cw <= 24)WTZ_EXTFR_CASE(24);
+	else if(Cw <= 26)WTZ_EXTFR_CASE(26);
+	else if(Cw <= 28)WTZ_EXTFR_CASE(28);
+	else WTZ_EXTFR_CASE(32);
 #undef WTZ_EXTFR_CASE
 	if(!consistent) return false;          /* mat / mis did not follow from the score: the job stays open for the general kernel (wtz_kernel_extjobs) */
 	if(lane == 0){ job->x = x; job->cigar = cg.a; job->cigar_len = cg.n; job->bad = (!ok || cg.bad); job->cells = cells; job->done = 5; }
@@ -388,12 +373,12 @@ WTZ_D bool wtz_extjob_run_fr(wtz_extjob_t *job, const wtz_params_t *Pm, wtz_pool
 }
 
 /* one wavefront per job */
-template<int TW, int CLO = 0, int CHI = 32>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WTZ_FR_OCC(CHI), 8))) wtz_kernel_extjobs_fr(wtz_extjob_t *jobs, const uint32_t *order, uint32_t n, const wtz_params_t *Pm, wtz_pool_t *pool, wtz_pool_t *tpool){
+template<int TW>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WTZ_OCC_EXTFR, 8))) wtz_kernel_extjobs_fr(wtz_extjob_t *jobs, const uint32_t *order, uint32_t n, const wtz_params_t *Pm, wtz_pool_t *pool, wtz_pool_t *tpool){
 	__shared__ uint64_t stb[TW];
 	const uint32_t b = blockIdx.x;
 	if(b >= n) return;
-	(void)wtz_extjob_run_fr<TW, CLO, CHI>(&jobs[order ? order[b] : b], Pm, pool, tpool, stb);
+	(void)wtz_extjob_run_fr<TW>(&jobs[order ? order[b] : b], Pm, pool, tpool, stb);
 }
 
 #endif /* __HIPCC__ */

@@ -24,8 +24,8 @@
  * arg-max column inside the winning run comes from per-lane match masks (a 16-bit compare on one half + an add with carry per register: first the group
  * maxima, then the four registers of one group), of which only the winning lane's two words go to the scalar unit.
  * Target: two bit planes in LDS (low / high bit of the base, 32 columns per word), so that "bases equal" is one dense bit per column: (P_lo ^ ~q_lo) & (P_hi ^ ~q_hi).
- * Trace: a NIBBLE per cell (the four decisions), eight cells per dword: half the trace bytes of the 32-bit form; wtz_shift_traceback_pk stages it into the
- * walker's byte window of wtz_shift_traceback.
+ * Trace: a NIBBLE per cell (the four decisions), eight cells per dword (registers 4q .. 4q+3 of the lane: run A's nibbles in bits 0..15, run B's in bits 16..31):
+ * half the trace bytes of the 32-bit form; wtz_shift_traceback_pk stages it into the walker's byte window of wtz_shift_traceback.
  */
 #ifndef WTZ_SW_FRAME16_H
 #define WTZ_SW_FRAME16_H
@@ -148,7 +148,7 @@ WTZ_D void wtz_pk_row(uint32_t (&hv)[C2], uint32_t (&ev)[C2], uint32_t (&zw)[(C2
 	});
 }
 
-/* traceback over the nibble trace of wtz_extend_shift_pk: wtz_shift_traceback<C, 64, false> with another staging step (dword q of lane l of a row holds the
+/* traceback over the nibble trace of wtz_extend_shift_pk: wtz_shift_traceback<C, 64> with another staging step (dword q of lane l of a row holds the
  * registers 4q .. 4q+3 of the lane: run A's nibbles in bits 0..15, run B's in bits 16..31) */
 template<int C2>
 WTZ_D bool wtz_shift_traceback_pk(wtz_aln_t &x, uint8_t **zchunk, const int32_t *zb, uint32_t zrow, uint32_t *lds, wtz_cigar_t &cigars, const wtz_tb_score *sc){
@@ -159,6 +159,9 @@ WTZ_D bool wtz_shift_traceback_pk(wtz_aln_t &x, uint8_t **zchunk, const int32_t 
 	static_assert(NDW <= 64 && ROWB <= 128, "window geometry");
 	uint32_t *S32 = lds; uint8_t *S8 = (uint8_t*)lds; uint8_t *Sd = S8 + 8192;
 	int32_t i_ = x.qe, j_ = x.te; uint32_t d_ = 0;
+#ifdef WTZ_EXP_NOTB
+	i_ = -1; j_ = -1;      /* diagnostic build: no traceback (results are wrong) */
+#endif
 	uint32_t run_op = 0xFFu, run_len = 0;
 	int32_t n_gap_runs = 0; bool consistent = true;
 	wtz_cigw_t Wr; Wr.v = &cigars; Wr.tail = 0;

@@ -505,15 +505,16 @@ WTZ_D void wtz_cigw_finish(wtz_cigw_t &w){ if(w.tail){ w.v->push(w.tail); w.tail
  * band-relative column order.  The walker tracks the band-relative column itself (a row's band start moves by 0..2 against the
  * row above: 64 deltas in LDS), leaves the block after 64 rows or through either edge of the window, and the next block is
  * staged around the cell it stands on.  Runs go through the register-tail writer and are reversed once at the end.
- * LDS: 8192 + 64 bytes at `tb` (the target words are dead by now). ---- */
-/* EQ = false (the frame form, wtz_sw_frame.h): the trace byte holds the four decisions only (bit 3 m<e, bit 2 max(m,e)<f, bit 1 E extended, bit 0 F extended); the walk
- * counts diagonal steps and gap runs, and matches / mismatches follow from the score: every gap run of the path was opened once (a run ends in the diagonal step
+ * LDS: 8192 + 64 bytes at `tb` (the target words are dead by now).
+ * The trace byte holds the four decisions only (bit 3 m<e, bit 2 max(m,e)<f, bit 1 E extended, bit 0 F extended; the "bases equal" bit of the round-4 register kernel
+ * went with that kernel); the walk counts diagonal steps and gap runs, and matches / mismatches follow from the score: every gap run of the path was opened once (a run ends in the diagonal step
  * of the cell it was opened from - kswx.h:175-183 opens from m, not from H - so two runs never touch), hence
  *     score - init = M*mat + X*mis + runs*O + E*(ins + del),   mat + mis = diagonal steps.
- * `sc` = {M, X, O, E, init_score (clamped)}; returns false when the identity does not come out in integers (never observed; the caller then leaves the job to the general kernel). */
+ * `sc` = {M, X, O, E, init_score (clamped)}; returns false when the identity does not come out in integers (never observed; the caller then leaves the job to the general kernel).
+ * wtz_shift_traceback_pk (wtz_sw_frame16.h) is this function with the nibble trace's staging step. ---- */
 struct wtz_tb_score { int32_t M, X, O, E, init; };
-template<int C, int NL, bool EQ = true>
-WTZ_D bool wtz_shift_traceback(wtz_aln_t &x, uint8_t **zchunk, const int32_t *zb, uint32_t zrow, uint64_t *tb, wtz_cigar_t &cigars, const wtz_tb_score *sc = NULL){
+template<int C, int NL>
+WTZ_D bool wtz_shift_traceback(wtz_aln_t &x, uint8_t **zchunk, const int32_t *zb, uint32_t zrow, uint64_t *tb, wtz_cigar_t &cigars, const wtz_tb_score *sc){
 	const int lane = (int)(threadIdx.x & 63);
 	constexpr int C4 = (C + 3) / 4;
 	constexpr int NLW = (128 / C) < NL ? (128 / C) : NL;     /* lanes of a row inside the window */
@@ -558,16 +559,10 @@ WTZ_D bool wtz_shift_traceback(wtz_aln_t &x, uint8_t **zchunk, const int32_t *zb
 			if(act){
 				#pragma unroll
 				for(int u = 0; u < 8; u++){
-					/* the kernel's 5 decision bits -> the walker's byte: bits 1:0 move from H, bits 3:2 from E, bits 5:4 from F, bit 7 bases equal */
+					/* the kernel's 4 decision bits -> the walker's byte: bits 1:0 move from H, bits 3:2 from E, bits 5:4 from F */
 					const uint32_t w = w8[u];
-					uint32_t v;
-					if constexpr(EQ){
-						const uint32_t a = (w >> 3) & 0x01010101u, b = (w >> 4) & 0x01010101u;
-						v = (a << 1) | (b & (a ^ 0x01010101u)) | (w & 0x04040404u) | ((w & 0x02020202u) << 4) | ((w & 0x01010101u) << 7);
-					} else {
-						const uint32_t a = (w >> 2) & 0x01010101u, b = (w >> 3) & 0x01010101u;
-						v = (a << 1) | (b & (a ^ 0x01010101u)) | ((w & 0x02020202u) << 1) | ((w & 0x01010101u) << 5);
-					}
+					const uint32_t a = (w >> 2) & 0x01010101u, b = (w >> 3) & 0x01010101u;
+					const uint32_t v = (a << 1) | (b & (a ^ 0x01010101u)) | ((w & 0x02020202u) << 1) | ((w & 0x01010101u) << 5);
 					const uint32_t pos = (uint32_t)(r8 + u) * 128u + pos0;
 					if constexpr((C & 3) == 0) S32[pos >> 2] = v;
 					else {
@@ -590,7 +585,7 @@ WTZ_D bool wtz_shift_traceback(wtz_aln_t &x, uint8_t **zchunk, const int32_t *zb
 				}
 				const int32_t sft = (int32_t)Sd[rr];
 				d_ = (zv >> (d_ << 1)) & 0x03;
-				if(d_ == 0){ if(!EQ || (zv & 0x80u)) x.mat++; else x.mis++; i_--; j_--; cc += sft - 1; }      /* !EQ: x.mat counts the diagonal steps until the end */
+				if(d_ == 0){ x.mat++; i_--; j_--; cc += sft - 1; }      /* x.mat counts the diagonal steps until the end */
 				else if(d_ == 1){ i_--; x.ins++; cc += sft; }
 				else { j_--; x.del++; cc--; }
 				if(d_ == run_op) run_len++;
@@ -606,12 +601,10 @@ WTZ_D bool wtz_shift_traceback(wtz_aln_t &x, uint8_t **zchunk, const int32_t *zb
 		if(j_ >= 0){ x.del += j_ + 1; wtz_cigw_push(Wr, 2, (uint32_t)(j_ + 1)); n_gap_runs++; }
 		wtz_cigw_finish(Wr);
 		wtz_cigar_reverse(cigars.a, cigars.n);
-		if constexpr(!EQ){
-			const int32_t nd = x.mat, MXd = sc->M - sc->X;
-			const long long S = (long long)x.score - sc->init - (long long)n_gap_runs * sc->O - (long long)sc->E * (x.ins + x.del) - (long long)sc->X * nd;
-			if(MXd == 0 || S % MXd != 0 || S / MXd < 0 || S / MXd > nd) consistent = false;
-			else { x.mat = (int32_t)(S / MXd); x.mis = nd - x.mat; }
-		}
+		const int32_t nd = x.mat, MXd = sc->M - sc->X;
+		const long long S = (long long)x.score - sc->init - (long long)n_gap_runs * sc->O - (long long)sc->E * (x.ins + x.del) - (long long)sc->X * nd;
+		if(MXd == 0 || S % MXd != 0 || S / MXd < 0 || S / MXd > nd) consistent = false;
+		else { x.mat = (int32_t)(S / MXd); x.mis = nd - x.mat; }
 		x.aln = x.mat + x.mis + x.ins + x.del; x.qe++; x.te++;
 	}
 	return __builtin_amdgcn_readfirstlane((int)consistent) != 0;

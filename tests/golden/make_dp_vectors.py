@@ -63,6 +63,16 @@ def pair(rng, nq, nt, err=0.15, related=True, homopolymers=False):
     return np.ascontiguousarray(q[:nq]), np.ascontiguousarray(t[:nt])
 
 
+def ext_geometry(qlen, tlen, W):
+    """wtz_ext_geometry (smartdenovo_amd/csrc/wtz_sw.h) for an exact band (W < 0): (w, rows, columns, band columns)"""
+    w = min(-W, max(qlen, tlen))
+    if qlen < tlen:
+        ql, tl = qlen, min(qlen + w, tlen)
+    else:
+        tl, ql = tlen, min(tlen + w, qlen)
+    return w, ql, tl, min(tl, 2 * w + 1)
+
+
 def call_ext(fn, q, t, init, W):
     a = Aln()
     cg = np.zeros(q.size + t.size + 8, dtype=np.uint32)
@@ -198,6 +208,20 @@ def main():
         q, t = pair(rng, 300, 310, homopolymers=True)
         add(2, "g_homo", q, t, W=50)
 
+    # ---------------- K-sw3, the band classes the first block leaves out (appended; a generator of its own, so that no draw above or below moves) ----------------
+    # Cw = band columns per lane = ceil((2W + 1) / 64) for sides longer than 2W; the one-wave frame forms compile one row body per class of two columns:
+    # Cw 6 .. 28 run as 32-bit C = Cw and packed C2 = Cw / 2 (odd C2: the byte-store staging of the nibble decoder), Cw 30 as C = 32 and C2 = 15
+    n_first = len(probs)
+    rng2 = np.random.default_rng(20261020)
+    for W, Cw in ((170, 6), (300, 10), (430, 14), (560, 18), (690, 22), (880, 28), (940, 30)):
+        for k in range(2):
+            L = int(rng2.integers(2 * W + 40, 2 * W + 200))
+            q, t = pair(rng2, L + int(rng2.integers(-30, 30)), L + int(rng2.integers(-30, 30)), err=0.15)
+            init = int(rng2.integers(0, 500))
+            w, ql, tl, n_col = ext_geometry(q.size, t.size, -W)
+            assert (n_col + 63) // 64 == Cw, (W, Cw, n_col)
+            add(0, "s_cw%d" % Cw, q, t, init=init, W=-W)
+
     # ---------------- expected outputs from the reference ----------------
     alns, cigs = [], []
     for p in probs:
@@ -213,13 +237,14 @@ def main():
     seqs, view = [], []
     for i, p in enumerate(probs):
         row = []
+        g = rng if i < n_first else rng2      # the appended block draws its views from its own generator too
         for side in ("q", "t"):
             L = p[side]
-            rev = int(rng.integers(0, 2))
-            strand = int(rng.choice([1, -1]))
-            fa, fb = int(rng.integers(0, 40)), int(rng.integers(0, 40))
+            rev = int(g.integers(0, 2))
+            strand = int(g.choice([1, -1]))
+            fa, fb = int(g.integers(0, 40)), int(g.integers(0, 40))
             seg = L if strand > 0 else L[::-1]
-            v = np.concatenate([rng.integers(0, 4, size=fa, dtype=np.uint8), seg, rng.integers(0, 4, size=fb, dtype=np.uint8)]).astype(np.uint8)
+            v = np.concatenate([g.integers(0, 4, size=fa, dtype=np.uint8), seg, g.integers(0, 4, size=fb, dtype=np.uint8)]).astype(np.uint8)
             frm = fa if strand > 0 else fa + L.size - 1
             if L.size == 0:
                 frm = min(fa, max(0, v.size - 1))
@@ -232,8 +257,7 @@ def main():
         view.append(row)
     meta = dict(scores=SCORES, classes=sorted(set(p["cls"] for p in probs)),
                 note="reads 2i / 2i+1 hold the query / target of problem i; view = (q_rev, q_from, q_strand, t_rev, t_from, t_strand)")
-    np.savez_compressed(
-        os.path.join(HERE, "dp_vectors.npz"),
+    arrays = dict(
         kind=np.array([p["kind"] for p in probs], dtype=np.int32),
         cls=np.array([p["cls"] for p in probs]),
         init=np.array([p["init"] for p in probs], dtype=np.int32),
@@ -249,6 +273,17 @@ def main():
         cig=np.concatenate(cigs).astype(np.uint32) if cigs else np.zeros(0, np.uint32),
         meta=np.array(json.dumps(meta)),
     )
+    out = os.path.join(HERE, "dp_vectors.npz")
+    if os.path.exists(out):      # problems are only ever appended: what is committed must be the prefix of what is written
+        old = np.load(out)
+        for name in old.files:
+            if name == "meta":
+                om = json.loads(str(old[name]))
+                assert om["scores"] == meta["scores"] and set(om["classes"]) <= set(meta["classes"])
+                continue
+            a, b = old[name], arrays[name]
+            assert a.shape[1:] == b.shape[1:] and a.shape[0] <= b.shape[0] and (a == b[:a.shape[0]]).all(), "committed array %s is not a prefix of the new one" % name
+    np.savez_compressed(out, **arrays)
     print("%d problems: %s" % (len(probs), {k: int(sum(1 for p in probs if p["kind"] == k)) for k in (0, 1, 2)}))
     print("size %.1f KB" % (os.path.getsize(os.path.join(HERE, "dp_vectors.npz")) / 1024))
 

@@ -32,12 +32,33 @@ def vec():
 
 def test_vectors_cover_every_shape_class(vec):
     want = {"s_c1", "s_c4", "s_c8", "s_c12", "s_c16", "s_c20", "s_c24", "s_c28", "s_c32", "s_short", "s_rows", "s_stop", "s_end", "s_homo", "s_wide",
-            "s_keyovf", "s_longt", "s_empty", "s_neginit", "f_w50", "f_w20", "f_w5", "f_w100", "f_w200", "f_long", "f_rows2048", "f_keyovf", "f_stop",
+            "s_keyovf", "s_longt", "s_empty", "s_neginit", "s_cw6", "s_cw10", "s_cw14", "s_cw18", "s_cw22", "s_cw28", "s_cw30", "f_w50", "f_w20", "f_w5", "f_w100", "f_w200", "f_long", "f_rows2048", "f_keyovf", "f_stop",
             "f_empty", "f_homo", "g_c1", "g_c2", "g_c4", "g_c8", "g_ring", "g_ringwide", "g_small", "g_long", "g_unrelated", "g_empty", "g_homo"}
     assert want <= set(vec.cls.tolist())
     # the views cover both strands and both walking directions on both sides
     assert {tuple(v) for v in vec.view[:, [0, 2]].tolist()} == {(0, 1), (0, -1), (1, 1), (1, -1)}
     assert {tuple(v) for v in vec.view[:, [3, 5]].tolist()} == {(0, 1), (0, -1), (1, 1), (1, -1)}
+
+
+def test_band_class_vectors_are_inside_both_frame_forms(vec):
+    """The s_cw<n> problems exist to reach the row bodies of n band columns per lane in BOTH one-wave frame forms (DP forms 5 and 7 must answer them,
+    tests/test_gpu_dp_forms.py): each has the band it is named for, two problems per class, and lies inside the 32-bit form's 2^20 envelope, its LDS words
+    and the packed form's 16-bit window (a) - none of them is declined for its values."""
+    from test_packed_window_model import geometry, pk_window
+    S = vec.meta["scores"]
+    seen = {}
+    for i in np.nonzero(np.char.startswith(vec.cls, "s_cw"))[0]:
+        w, ql, tl = geometry(int(vec.qlen[i]), int(vec.tlen[i]), int(vec.W[i]))
+        n_col = min(tl, 2 * w + 1)
+        assert (n_col + 63) // 64 == int(str(vec.cls[i])[4:]), "problem %d (%s)" % (i, vec.cls[i])
+        init = max(int(vec.init[i]), 0)
+        assert init + abs(S["M"]) * min(ql, tl) + (ql + tl + 4) * abs(S["E"]) + 10000 + abs(S["X"]) + abs(S["O"]) + 16 < (1 << 20)       # wtz_extjob_run_fr
+        assert (tl + 63) // 32 + 1 <= 1032 and (tl + 31) // 32 + 3 <= 1032 and (ql + 63) // 64 <= 1024
+        assert (S["M"], S["X"], S["O"], S["E"]) == (2, -5, -3, -1)       # the scores pk_window is written for
+        win = pk_window(init, ql, tl)
+        assert win is not None and win[1] == -10000 and win[2] == -(1 << 30), "problem %d (%s): not in window (a)" % (i, vec.cls[i])
+        seen[str(vec.cls[i])] = seen.get(str(vec.cls[i]), 0) + 1
+    assert seen == {"s_cw%d" % n: 2 for n in (6, 10, 14, 18, 22, 28, 30)}
 
 
 @pytest.mark.parametrize("kind", [0, 1, 2])

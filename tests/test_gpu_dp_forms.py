@@ -61,9 +61,11 @@ def check(vec, idx, out, cigs, kind, form, must):
 # 5 = one-wave kernel in the anti-diagonal frame (round 5, the product's 32-bit one-wave form: band <= 64 x 32 columns, target <= 1032 LDS words, key range),
 # 7 = the frame form with two 16-bit cells per register (round 6: the product's first choice; same band envelope, values inside a 16-bit window).
 # 1 (round-4 one-wave register kernel), 2 (round-4 four-wave kernel) and 6 (frame form on four wavefronts) have been removed; their numbers are not reused.
+# s_cw<n>: n band columns per lane, the classes between those above: 32-bit row bodies 6, 10, 14, 18, 22, 28 and 32 (for 30), packed 3, 5, 7, 9, 11, 14, 15
+SHIFT_CW = ("s_cw6", "s_cw10", "s_cw14", "s_cw18", "s_cw22", "s_cw28", "s_cw30")
 SHIFT_MUST = {
-    5: {"s_c1", "s_c4", "s_c8", "s_c12", "s_c16", "s_c20", "s_c24", "s_c28", "s_c32", "s_short", "s_rows", "s_stop", "s_end", "s_homo", "s_neginit"},
-    7: {"s_c1", "s_c4", "s_c8", "s_c12", "s_c16", "s_c20", "s_c24", "s_c28", "s_c32", "s_short", "s_rows", "s_stop", "s_end", "s_homo", "s_neginit"},
+    5: {"s_c1", "s_c4", "s_c8", "s_c12", "s_c16", "s_c20", "s_c24", "s_c28", "s_c32", "s_short", "s_rows", "s_stop", "s_end", "s_homo", "s_neginit"} | set(SHIFT_CW),
+    7: {"s_c1", "s_c4", "s_c8", "s_c12", "s_c16", "s_c20", "s_c24", "s_c28", "s_c32", "s_short", "s_rows", "s_stop", "s_end", "s_homo", "s_neginit"} | set(SHIFT_CW),
 }
 
 
