@@ -25,6 +25,8 @@
  *   wtz_pairs_seed + wtz_pairs_align with params.aux_strand = 1
  *                        <- align_hzmaux, the pair routine of wtgbo   hzm_aln.h:1684-1775 (its caller wtgbo.c:37-56 orients the read first:
  *                           the host uploads every read and its reverse complement, smartdenovo_amd/csrc/host/wtgbo_main.c)
+ *   wtz_pairs_seed_region <- the same with beg / end: query_single_read_seeds_by_region   hzm_aln.h:117-171, 1690-1693 (wtmsa.c:448-477, wtjnt)
+ *   wtz_hzmaux_batch     <- align_hzmaux as one call per batch of (target, read, beg, end)  hzm_aln.h:1684-1775
  *
  * Everything returned is integer and bit-exact against `wtzmo -t 1`.  The order-dependent state of
  * the reference (closed pairs, contained-read masking, per-read coverage: wtzmo.c:806-822, 1065-1100,
@@ -196,6 +198,18 @@ int  wtz_batch_begin(wtz_ctx_t *ctx);
 /* A5/A6/A7 for n (query, candidate) pairs. Results stay on the device for wtz_pairs_windows / wtz_pairs_align. */
 int  wtz_pairs_seed(wtz_ctx_t *ctx, const uint32_t *qid, const uint32_t *cid, uint32_t n, wtz_pair_summary_t *out);
 
+/* wtz_pairs_seed in align_hzmaux's REGION form (hzm_aln.h:1684-1699 with beg / end set, as wtmsa calls it for every read of a layout: wtmsa.c:448-477): pair i
+ * matches the z-mers of read cid[i] against the interval [beg[i], end[i]) of the indexed read qid[i] only - query_single_read_seeds_by_region, hzm_aln.h:117-171.
+ * Defaults per pair as hzm_aln.h:1690-1691: beg < 0 -> 0, end <= 0 -> the length of read qid[i]; an end behind the read is not clamped (it excludes nothing);
+ * beg >= end after the defaults matches nothing (n_hits = 0, gate = 0).  Inside the walk of an indexed z-mer's occurrences (in `off` order, hzm_aln.h:101)
+ * an occurrence in front of beg is skipped and the FIRST one that ends behind end ends the walk (hzm_aln.h:160-161: a break - later occurrences of that z-mer are
+ * lost even where a shorter homopolymer-expanded length would fit); the length test (hzm_aln.h:162) comes after both.  The second interval test of
+ * filter_by_region_hzmps (hzm_aln.h:1194) cannot fail behind that one, and its read-side test cannot fail at all (a z-mer lies inside its read).
+ * Everything after the matches is blind to the interval, as in the reference: wtz_pairs_windows / wtz_pairs_align / wtz_fetch_cigars follow unchanged, the end
+ * extensions run into the whole indexed read (hzm_aln.h:1714) and tb / te of the alignment may lie outside [beg, end).
+ * Needs params.aux_strand = 1 and the zmo engine (params.dot_matrix = 0): WTZ_E_ARG otherwise.  With (0, 0) for every pair it returns what wtz_pairs_seed returns. */
+int  wtz_pairs_seed_region(wtz_ctx_t *ctx, const uint32_t *qid, const uint32_t *cid, const int32_t *beg, const int32_t *end, uint32_t n, wtz_pair_summary_t *out);
+
 /* Chain windows of the last wtz_pairs_seed, packed in (pair, strand) order: sum of nwin[] entries. */
 int  wtz_pairs_windows(wtz_ctx_t *ctx, wtz_winbox_t *wins, uint64_t n_wins);
 
@@ -360,6 +374,23 @@ typedef struct { int32_t qb, tb; uint32_t cigar_len, pad; uint64_t cigar_off; } 
 typedef struct { uint64_t text_off; uint32_t cols, pad; } wtz_pwtext_result_t;
 int  wtz_pwtext_batch(wtz_ctx_t *ctx, const wtz_dp_problem_t *problems, const wtz_pwtext_in_t *in, uint32_t n, const uint32_t *cigar, uint64_t n_ops,
                       wtz_pwtext_result_t *out, char *text, uint64_t text_cap);
+
+/* align_hzmaux(aux, rid, rdseq, NULL, rdlen, beg, end, params.refine, params.min_id) (hzm_aln.h:1684-1775) for n (target read tid[i], query read rid[i]) pairs
+ * in one call - what wtmsa runs per read of a layout against a region of the backbone (wtmsa.c:448-477) and, with (0, -1), per N read:
+ *   wtz_pairs_seed_region (hzm_aln.h:1690-1699) -> wtz_pairs_align of the pairs with windows and a chain of at least zovl (hzm_aln.h:1700-1714; with
+ *   params.refine kswx_refine_alignment, hzm_aln.h:1721-1729, band params.w) -> the gates of hzm_aln.h:1715-1718 in the reference's float arithmetic (with
+ *   params.refine the device applied them in front of the refinement) -> the CIGARs of the hits.
+ * out[i]: found = align_hzmaux's return value; the kswx_t aux->hit (hzm_aln.h:1730; all 0 without a hit); cigar_off / cigar_len of its operations
+ * (len << 4 | op, op 0 both, 1 query only, 2 target only: hzm_aln.h:1737-1772) in `cigar`, hits packed in pair order.  cigar = NULL with cigar_cap = 0: the
+ * records alone.  A cigar_cap smaller than the sum of the hits' cigar_len is WTZ_E_ARG, the text names the words needed and out[] is complete (offsets
+ * included), so the caller can allocate and call again.
+ * Needs params.aux_strand = 1 and the zmo engine (WTZ_E_ARG), and both reads of every pair in the z-index (wtz_zindex_build, or wtz_zindex_build_subset of the
+ * targets AND the queries: the device reads a query's position-ordered z-mers from the index too) - WTZ_E_STATE otherwise.  params.O is the one gap-open
+ * cost of every device DP: I = D = O.  WTZ_E_POOL: nothing was returned, use fewer pairs per call (the halving loop of the batch tools, ht_halving).
+ * The call ends the batch it ran, on success and on failure alike: the main pool goes back empty, wtz_pairs_windows / wtz_pairs_align need a new wtz_pairs_seed. */
+typedef struct { int32_t found, score, tb, te, qb, qe, aln, mat, mis, ins, del; uint32_t cigar_len; uint64_t cigar_off; } wtz_hzmaux_result_t;
+int  wtz_hzmaux_batch(wtz_ctx_t *ctx, const uint32_t *tid, const uint32_t *rid, const int32_t *beg, const int32_t *end, uint32_t n,
+                      wtz_hzmaux_result_t *out, uint32_t *cigar, uint64_t cigar_cap);
 
 /* Scratch accounting, so that the caller can size its batches to the pool instead of discovering the limit by WTZ_E_POOL:
  * the context's scratch is cut into a main pool (everything that lives for the batch: match lists, windows, CIGARs) and a transient

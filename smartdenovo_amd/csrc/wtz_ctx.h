@@ -53,7 +53,9 @@ struct wtz_ctx {
 	struct zslot_t {
 		std::vector<std::pair<void*, size_t> > parked, live;
 		uint64_t *zoff = NULL; uint64_t n_z = 0; wtz_zindex_t Z; bool have = false; bool sub = false; uint64_t sub_cap = 0;      /* sub: the slot holds a subset of the reads (rebuilt per batch) */
+		std::vector<uint32_t> members;      /* sub: the ids of the reads the slot holds, ascending (holds()) */
 		zslot_t(){ memset(&Z, 0, sizeof Z); }
+		bool holds(uint32_t r) const { return have && (!sub || std::binary_search(members.begin(), members.end(), r)); }
 	} zs[2];
 #ifndef WTZ_EMUL
 	hipStream_t stream = 0;
@@ -268,7 +270,7 @@ static void free_zindex(wtz_ctx *c){
 	for(int k = 0; k < 2; k++){
 		wtz_ctx::zslot_t *z = &c->zs[k];
 		if(!c->shares_indexes){ zpark_all(z); zflush_parked(z); }      /* every z-index array comes from zalloc */
-		z->zoff = NULL; memset(&z->Z, 0, sizeof z->Z); z->have = false; z->sub = false; z->sub_cap = 0; z->n_z = 0;
+		z->zoff = NULL; memset(&z->Z, 0, sizeof z->Z); z->have = false; z->sub = false; z->sub_cap = 0; z->n_z = 0; z->members.clear();
 	}
 }
 static void free_batch(wtz_ctx *c){ c->n_pairs = 0; c->n_items = 0; c->have_pairs = false; c->have_items = false; }
@@ -329,7 +331,7 @@ extern "C" int wtz_ctx_clone(wtz_ctx_t *p, uint64_t pool_bytes, wtz_ctx_t **out)
 	c->bits = p->bits; c->n_words = p->n_words; c->rdoff = p->rdoff; c->rdlen = p->rdlen; c->n_reads = p->n_reads; c->h_rdlen = p->h_rdlen;
 	c->ktab = p->ktab; c->kmask = p->kmask; c->kseeds = p->kseeds; c->n_kocc = p->n_kocc;
 	c->idx_beg = p->idx_beg; c->idx_end = p->idx_end; c->idx_len_sorted = p->idx_len_sorted;
-	for(int k = 0; k < 2; k++){ c->zs[k].zoff = p->zs[k].zoff; c->zs[k].n_z = p->zs[k].n_z; c->zs[k].Z = p->zs[k].Z; c->zs[k].have = p->zs[k].have; }
+	for(int k = 0; k < 2; k++){ c->zs[k].zoff = p->zs[k].zoff; c->zs[k].n_z = p->zs[k].n_z; c->zs[k].Z = p->zs[k].Z; c->zs[k].have = p->zs[k].have; c->zs[k].sub = p->zs[k].sub; c->zs[k].members = p->zs[k].members; }
 	*out = c;
 	return WTZ_OK;
 }

@@ -10,12 +10,13 @@
  *   wtz_dev.h                      device layer, both back ends: errors, launchers, per-call arena, dev_*, timer, sort and scan
  *   wtz_ctx.h                      struct wtz_ctx, its switches, the two scratch pools, create / clone / destroy
  *   wtz_lib_index.h                reads upload and ingest, k-mer index, z-mer index, candidates
- *   wtz_lib_pairs.h                wtz_pairs_seed, wtz_pairs_windows
+ *   wtz_lib_pairs.h                wtz_pairs_seed, wtz_pairs_seed_region, wtz_pairs_windows
  *   wtz_lib_align.h                wtz_pairs_align: lane pipelines, chained K-sw1, K-sw2, K-sw3 extension jobs, fused stitch
  *   wtz_lib_fetch.h                CIGAR fetch and text rendering
  *   wtz_lib_batch.h                the skeleton of the batch services, each step once; wtz_extend_batch, wtz_local_batch, wtz_kext_batch, wtz_align_batch
  *   wtz_lib_glob.h                 wtz_global_batch, wtz_alignx_batch and the CIGAR hand-out they share (included by wtz_lib_batch.h)
  *   wtz_lib_pwtext.h               wtz_pwtext_batch (included by wtz_lib_batch.h)
+ *   wtz_lib_hzmaux.h               wtz_hzmaux_batch (included by wtz_lib_batch.h)
  *   wtz_testdp.h                   the test-only wtz_test_dp (included by wtz_lib_batch.h)
  *
  * Execution model: every stage is a flat grid of independent tasks (one lane, wavefront or workgroup per read / query / pair /
@@ -69,6 +70,7 @@ struct K_pair;
 struct K_pair_dm;
 struct K_pair_zbig;
 struct K_pair_big;
+struct K_pair_region;
 struct K_refine;
 struct K_pack_ascii;
 struct K_pack_fix;

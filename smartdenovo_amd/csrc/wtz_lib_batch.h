@@ -1,7 +1,8 @@
 /*
  * wtz_lib_batch.h — the DP routines as batch services for callers that hold their own problems: wtz_extend_batch (K-sw3), wtz_local_batch (K-local),
  * wtz_kext_batch (K-kext), wtz_align_batch (K-local + K-kext), through wtz_lib_glob.h wtz_global_batch (K-glob) and wtz_alignx_batch (all three), through
- * wtz_lib_pwtext.h wtz_pwtext_batch (K-pwtext) and, through wtz_testdp.h, the test-only wtz_test_dp.  Included by wtz_lib.cpp.
+ * wtz_lib_pwtext.h wtz_pwtext_batch (K-pwtext), through wtz_lib_hzmaux.h wtz_hzmaux_batch (the pair stages behind one call) and, through wtz_testdp.h, the test-only
+ * wtz_test_dp.  Included by wtz_lib.cpp.
  *
  * The skeleton they are written against stands first, each step once: BATCH_ARGS / batch_count / batch_begin (a call before it looks at a problem), batch_scores,
  * batch_order, batch_upload / batch_fetch (the two ends of a launch group), form_dispatch / for_each_form, pack_runs, pool_fail, batch_leave.
@@ -360,4 +361,5 @@ static int align_stages(wtz_ctx *c, const char *entry, const std::vector<uint64_
 
 #include "wtz_lib_glob.h"
 #include "wtz_lib_pwtext.h"
+#include "wtz_lib_hzmaux.h"
 #include "wtz_testdp.h"

@@ -354,6 +354,7 @@ static int zindex_build_impl(wtz_ctx_t *c, const uint32_t *members, uint32_t nm,
 		z->sub_cap = subset ? cap : 0;
 	}
 	z->sub = subset;
+	z->members.assign(members, members + (subset ? nm : 0));
 	z->Z = Z;
 	{
 		/* chunks of consecutive reads, so that the temporaries (sort keys and their double buffer, run flags / lengths / ranks: 32 B per z-mer beside the 25 B the

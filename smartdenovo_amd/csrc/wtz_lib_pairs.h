@@ -1,6 +1,6 @@
 /*
  * wtz_lib_pairs.h — the per-batch pair stages in front of the alignment: wtz_batch_begin, wtz_pairs_seed (K_pair and the launches that finish what it
- * leaves) and wtz_pairs_windows.  Included by wtz_lib.cpp.
+ * leaves), wtz_pairs_seed_region (the same with one interval of the indexed read per pair: K_pair_region) and wtz_pairs_windows.  Included by wtz_lib.cpp.
  */
 #ifndef WTZ_PAIR_DM_LDS_TIER2
 #define WTZ_PAIR_DM_LDS_TIER2 49152u
@@ -40,7 +40,9 @@ static void wtz_crumbs_dump(int sig){
 }
 #endif
 
-extern "C" int wtz_pairs_seed(wtz_ctx_t *c, const uint32_t *qid, const uint32_t *cid, uint32_t n, wtz_pair_summary_t *out){
+/* wtz_pairs_seed (beg == NULL) and wtz_pairs_seed_region (one interval [beg[i], end[i]) of read qid[i] per pair, defaults applied by the caller): the
+ * two differ in the first launch only, K_pair or K_pair_region */
+static int pairs_seed_run(wtz_ctx_t *c, const char *who, const uint32_t *qid, const uint32_t *cid, const int32_t *beg, const int32_t *end, uint32_t n, wtz_pair_summary_t *out){
 	if(!c || !c->zs[0].have || (n && (!qid || !cid || !out))) return wtz_fail(WTZ_E_ARG, "z-index not built / null argument");
 	CTX_ENTER(c);
 	free_batch(c);
@@ -49,10 +51,19 @@ extern "C" int wtz_pairs_seed(wtz_ctx_t *c, const uint32_t *qid, const uint32_t 
 	for(uint32_t i = 0; i < n; i++) if(qid[i] >= c->n_reads || cid[i] >= c->n_reads) return wtz_fail(WTZ_E_ARG, "pair %u: read id out of range", i);
 	CHK(reserve_pairs(c, n));
 	CHK(dev_h2d(c->d_qid, qid, (size_t)n * 4)); CHK(dev_h2d(c->d_cid, cid, (size_t)n * 4));
+	int32_t *d_beg = NULL, *d_end = NULL;
+	if(beg){
+		/* the defaults of hzm_aln.h:1690-1691: beg < 0 -> 0, end <= 0 -> the length of the indexed read; an end behind the read stays as it is (it excludes nothing) */
+		std::vector<int32_t> b(n), e(n);
+		for(uint32_t i = 0; i < n; i++){ b[i] = beg[i] < 0 ? 0 : beg[i]; e[i] = end[i] <= 0 ? (int32_t)c->h_rdlen[qid[i]] : end[i]; }
+		CHK(dev_alloc((void**)&d_beg, (size_t)n * 4)); CHK(dev_h2d(d_beg, b.data(), (size_t)n * 4));
+		CHK(dev_alloc((void**)&d_end, (size_t)n * 4)); CHK(dev_h2d(d_end, e.data(), (size_t)n * 4));
+	}
 	const wtz_env_t V = ctx_env(c); const uint32_t *dq = c->d_qid, *dc = c->d_cid; wtz_pairres_t *dr = c->d_pairres;
 	wtz_timer tm; tm.start();
 	wtz_timer t1; t1.start();
-	STAGE(c, "K_pair");
+	const char *kname = beg ? "K_pair_region" : "K_pair";
+	STAGE(c, kname);
 #if defined(WTZ_DEBUG_CRUMBS) && !defined(WTZ_EMUL)
 	unsigned int *h_crumbs = NULL;
 	if(getenv("WTZ_DEBUG_CRUMBS")){
@@ -91,9 +102,14 @@ extern "C" int wtz_pairs_seed(wtz_ctx_t *c, const uint32_t *qid, const uint32_t 
 #endif
 	const uint64_t n64 = n - nh; const uint64_t nh64 = nh;
 #ifdef WTZ_EMUL
+	if(beg) CHK(wtz_launch_coop<K_pair_region>(n, [=] WTZ_LAMBDA (uint64_t b){ wtz_task_pair<-1, true, true>((uint32_t)b, V, dq, dc, dr, d_beg, d_end); }, WTZ_PAIR_LDS_BYTES));
+	else
 	CHK(wtz_launch_coop<K_pair>(n, [=] WTZ_LAMBDA (uint64_t b){ (void)xg; (void)n64; (void)nh64; (void)d_ord; wtz_task_pair<-1>((uint32_t)b, V, dq, dc, dr); }, c->P.dot_matrix ? WTZ_PAIR_DM_LDS_BYTES : WTZ_PAIR_LDS_BYTES));
 #else
-	if(c->P.dot_matrix){
+	if(beg){
+		/* the pairs in the caller's order: the pairs of a layout share ONE query table, the backbone's, so there is nothing for the XCD mapping of K_pair to keep together */
+		CHK(wtz_launch_coop<K_pair_region>(n, [=] WTZ_LAMBDA (uint64_t b){ wtz_task_pair<0, true, true>((uint32_t)b, V, dq, dc, dr, d_beg, d_end); }, WTZ_PAIR_LDS_BYTES));
+	} else if(c->P.dot_matrix){
 		CHK(wtz_launch_coop<K_pair_dm>(n, [=] WTZ_LAMBDA (uint64_t b){
 			uint64_t t = b;
 			if(b >= nh64){ const uint64_t b2 = b - nh64; t = b2; if(xg){ const uint64_t per = 8ull * xg, full = n64 / per * per; if(b2 < full){ const uint64_t r = b2 % per; t = b2 - r + (r & 7u) * xg + (r >> 3); } } t += nh64; }
@@ -127,7 +143,7 @@ extern "C" int wtz_pairs_seed(wtz_ctx_t *c, const uint32_t *qid, const uint32_t 
 	}
 #endif
 	CHK(dev_sync());
-	{ const double ms1 = t1.stop(); if(c->sw.profile) fprintf(stderr, "[pair-profile] K_pair first launch: %u pairs, %.1f ms\n", n, ms1); }
+	{ const double ms1 = t1.stop(); if(c->sw.profile) fprintf(stderr, "[pair-profile] %s first launch: %u pairs, %.1f ms\n", kname, n, ms1); }
 	c->n_pairs = n; c->h_pairres.resize(n); c->have_pairs = true;
 	CHK(dev_d2h(c->h_pairres.data(), c->d_pairres, (size_t)n * sizeof(wtz_pairres_t)));
 #ifndef WTZ_EMUL
@@ -172,7 +188,7 @@ extern "C" int wtz_pairs_seed(wtz_ctx_t *c, const uint32_t *qid, const uint32_t 
 	}
 	c->cnt.ms_pairs += tm.stop(); c->cnt.n_pairs += n;
 	for(uint32_t i = 0; i < n; i++) c->cnt.bytes_zmer_algo += (uint64_t)c->h_rdlen[cid[i]] / 4 + 16ull * c->h_pairres[i].n_hits;
-	CHK(pool_check(c, "wtz_pairs_seed"));
+	CHK(pool_check(c, who));
 	if(c->sw.profile){
 		uint64_t sum[4] = {0, 0, 0, 0}; uint32_t mx[4] = {0, 0, 0, 0}, arg = 0;
 		for(uint32_t i = 0; i < n; i++){ for(int k = 0; k < 4; k++){ sum[k] += c->h_pairres[i].tick[k]; if(c->h_pairres[i].tick[k] > mx[k]){ mx[k] = c->h_pairres[i].tick[k]; if(k == 3) arg = i; } } }
@@ -182,13 +198,26 @@ extern "C" int wtz_pairs_seed(wtz_ctx_t *c, const uint32_t *qid, const uint32_t 
 	}
 	for(uint32_t i = 0; i < n; i++){
 		const wtz_pairres_t &r = c->h_pairres[i];
-		if(r.bad) return wtz_fail(WTZ_E_POOL, "wtz_pairs_seed: pair %u ran out of scratch", i);
+		if(r.bad) return wtz_fail(WTZ_E_POOL, "%s: pair %u ran out of scratch", who, i);
 		wtz_pair_summary_t s; memset(&s, 0, sizeof s);
 		s.n_hits = r.n_hits; s.gate = r.gate; s.ovl[0] = r.ovl[0]; s.ovl[1] = r.ovl[1]; s.nwin[0] = r.nwin[0]; s.nwin[1] = r.nwin[1];
 		s.dm_score = r.dm_score; s.dm_qb = r.dm_qb; s.dm_qe = r.dm_qe; s.dm_tb = r.dm_tb; s.dm_te = r.dm_te; s.dm_dir = r.dm_dir;
 		out[i] = s;
 	}
 	return WTZ_OK;
+}
+extern "C" int wtz_pairs_seed(wtz_ctx_t *c, const uint32_t *qid, const uint32_t *cid, uint32_t n, wtz_pair_summary_t *out){
+	return pairs_seed_run(c, "wtz_pairs_seed", qid, cid, NULL, NULL, n, out);
+}
+/* align_hzmaux's form of the pair stages wants params.aux_strand = 1 and the zmo engine */
+static int region_args(const wtz_ctx *c, const char *who){
+	if(c && (c->P.aux_strand == 0 || c->P.dot_matrix != 0)) return wtz_fail(WTZ_E_ARG, "%s: needs params.aux_strand = 1 and the zmo engine (align_hzmaux, hzm_aln.h:1684-1775)", who);
+	return WTZ_OK;
+}
+extern "C" int wtz_pairs_seed_region(wtz_ctx_t *c, const uint32_t *qid, const uint32_t *cid, const int32_t *beg, const int32_t *end, uint32_t n, wtz_pair_summary_t *out){
+	CHK(region_args(c, "wtz_pairs_seed_region"));
+	if(n && (!beg || !end)) return wtz_fail(WTZ_E_ARG, "null argument");
+	return pairs_seed_run(c, "wtz_pairs_seed_region", qid, cid, beg, end, n, out);
 }
 
 extern "C" int wtz_pairs_windows(wtz_ctx_t *c, wtz_winbox_t *wins, uint64_t n_wins){

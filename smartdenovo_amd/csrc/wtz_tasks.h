@@ -59,9 +59,13 @@ __device__ unsigned int *wtz_crumbs = NULL;
 /* ZBIG (zmo): the window scans may use a workspace in the pool when a range does not fit the LDS slice.  The first launch runs without that body (its registers
  * and code would be carried by every pair) and marks the few pairs that need it (dm_dir = WTZ_PAIR_NEEDS_ZBIG); a second launch finishes them. */
 #define WTZ_PAIR_NEEDS_ZBIG (-3)
-template<int ENGINE = -1, bool ZBIG = true>
-WTZ_HD void wtz_task_pair(uint32_t t, const wtz_env_t &V, const uint32_t *qid, const uint32_t *cid, wtz_pairres_t *res){
+/* REGION: align_hzmaux with beg / end (wtmsa's call, wtmsa.c:448-477): the z-mer matches of pair t are those of the interval [reg_beg[t], reg_end[t]) of the
+ * query, the indexed side (wtz_zmatch_coop<true>); the host has applied the defaults of hzm_aln.h:1690-1691.  Everything behind the matches is blind to the
+ * interval, as in the reference (hzm_aln.h:1696-1718).  A launch of its own (wtz_pairs_seed_region): the form without an interval does not carry the test. */
+template<int ENGINE = -1, bool ZBIG = true, bool REGION = false>
+WTZ_HD void wtz_task_pair(uint32_t t, const wtz_env_t &V, const uint32_t *qid, const uint32_t *cid, wtz_pairres_t *res, const int32_t *reg_beg = NULL, const int32_t *reg_end = NULL){
 	const wtz_params_t *P = V.P;
+	const int32_t rtb = REGION ? reg_beg[t] : 0, rte = REGION ? reg_end[t] : 0;
 	const bool dm = ENGINE < 0 ? (P->dot_matrix != 0) : (ENGINE == 1);
 	const uint32_t q = qid[t], c = cid[t];
 	wtz_pairres_t r; memset(&r, 0, sizeof r);
@@ -75,9 +79,9 @@ WTZ_HD void wtz_task_pair(uint32_t t, const wtz_env_t &V, const uint32_t *qid, c
 	WTZ_CRUMB(t, 1);
 	const bool aux = P->aux_strand != 0;                     /* align_hzmaux's form of the pair stages (wtgbo): strand 0 only, no n_hits gate */
 #if defined(__HIP_DEVICE_COMPILE__)
-	const bool ok0 = wtz_zmatch_coop(V.ZQ, V.Z, q, c, V.R.rdlen[c], P->max_kmer_var, V.pool, &hits, &n, aux, (uint32_t*)wtz_wave_scratch(), dm ? (uint32_t)WTZ_PAIR_DM_LDS_BYTES : (uint32_t)WTZ_PAIR_LDS_BYTES);      /* the LDS slice is free until the first ordering */
+	const bool ok0 = wtz_zmatch_coop<REGION>(V.ZQ, V.Z, q, c, V.R.rdlen[c], P->max_kmer_var, V.pool, &hits, &n, aux, (uint32_t*)wtz_wave_scratch(), dm ? (uint32_t)WTZ_PAIR_DM_LDS_BYTES : (uint32_t)WTZ_PAIR_LDS_BYTES, rtb, rte);      /* the LDS slice is free until the first ordering */
 #else
-	const bool ok0 = wtz_zmatch_coop(V.ZQ, V.Z, q, c, V.R.rdlen[c], P->max_kmer_var, V.pool, &hits, &n, aux);
+	const bool ok0 = wtz_zmatch_coop<REGION>(V.ZQ, V.Z, q, c, V.R.rdlen[c], P->max_kmer_var, V.pool, &hits, &n, aux, NULL, 0, rtb, rte);
 #endif
 	/* the same in every lane by construction; said explicitly, the early returns below are scalar branches and the window merge after them is not a masked region */
 	const bool ok = wtz_coop_bcast32(ok0 ? 1u : 0u) != 0;

@@ -59,9 +59,19 @@ WTZ_HD bool wtz_zmatch(const wtz_zindex_t &ZQ, const wtz_zindex_t &ZC, uint32_t 
  * COMPACTS the ones whose bit is set (ballot ranks: order kept); only those - a fifth - are searched.  A false positive is searched and
  * found absent like before; the emitted matches and their order are unchanged.  `lds` == NULL (host emulation) or a query too long for
  * the bitmap: every candidate z-mer is a survivor.
- * Returns the match list through *out / *n_out on every lane; false when the pool is exhausted. */
+ * Returns the match list through *out / *n_out on every lane; false when the pool is exhausted.
+ * REGION: query_single_read_seeds_by_region (hzm_aln.h:117-171) with qb = 0, qe = the candidate's length and the interval [tb, te) on the query, the indexed
+ * side (align_hzmaux with beg / end, hzm_aln.h:1690-1693; the defaults of hzm_aln.h:1690-1691 are the caller's).  The reference tests every occurrence of the
+ * indexed z-mer inside its walk of the occurrence list (hzm_aln.h:158-168): `off < tb` is a continue, `off + len > te` a BREAK, both in front of the length
+ * test.  The list is in `off` order (hzm_aln.h:101), so the continues skip a prefix of the run and the break cuts its tail at the first occurrence that ends
+ * behind te - later ones that would fit again (a shorter homopolymer-expanded len) are lost with it.  Here that is done where a survivor's run (first, cnt)
+ * is looked up, by the lane that holds the survivor, as two binary searches: for the end of the prefix, and for the first offender - off + len is the z-mer's last
+ * base + 1 (capped: off + 0xFFFF; hzm_aln.h:98-99) and never decreases along a run, so the first offender is where the reference's walk breaks.  What is cut never enters
+ * the flat list, so a read against a slice of a long backbone pays for the slice.  The candidate-side cap (`ok`, hzm_aln.h:154-157) counts in front of the
+ * interval tests in the reference and is a property of the candidate alone here: unchanged.  REGION = false compiles to the body it was before. */
+template<bool REGION = false>
 WTZ_HD bool wtz_zmatch_coop(const wtz_zindex_t &ZQ, const wtz_zindex_t &ZC, uint32_t q, uint32_t c, uint32_t clen, uint32_t max_var, wtz_pool_t *pool, wtz_zhit_t **out, uint32_t *n_out, bool same_strand = false,
-		uint32_t *lds = NULL, uint32_t lds_bytes = 0){
+		uint32_t *lds = NULL, uint32_t lds_bytes = 0, int32_t tb = 0, int32_t te = 0){
 	const uint64_t qo = ZQ.zoff[q], co = ZC.zoff[c];      /* ZQ: the index holding the query's table (A5), ZC: the one holding the candidate's position-ordered z-mers (the same index unless the caller split them) */
 	const uint32_t cn = (uint32_t)(ZC.zoff[c + 1] - co), qd = ZQ.dn[q];
 	const uint32_t *dmer = ZQ.dmer + qo;
@@ -138,6 +148,14 @@ WTZ_HD bool wtz_zmatch_coop(const wtz_zindex_t &ZQ, const wtz_zindex_t &ZC, uint
 			const uint32_t si = s0 + u * WTZ_NLANES + lane;
 			uint32_t cnt = 0, first = 0;
 			if(act[u] && lo[u] < qd && dmer[lo[u]] == m[u]){ first = ZQ.dfirst[qo + lo[u]]; cnt = ZQ.dcnt[qo + lo[u]]; }
+			if(REGION && cnt){
+				const uint32_t *run = ZQ.sidx + qo + first;
+				uint32_t a = 0, b = cnt;
+				while(a < b){ const uint32_t mid = (a + b) >> 1; if((int32_t)(ZQ.pos[qo + run[mid]] >> 1) < tb) a = mid + 1; else b = mid; }      /* hzm_aln.h:160 */
+				uint32_t e = cnt;
+				for(b = a; b < e; ){ const uint32_t mid = (b + e) >> 1, qi = run[mid]; if((int32_t)(ZQ.pos[qo + qi] >> 1) + (int32_t)ZQ.len[qo + qi] > te) e = mid; else b = mid + 1; }      /* hzm_aln.h:161: the first offender */
+				first += a; cnt = e - a;
+			}
 			uint32_t chunk; const uint32_t o = nflat + wtz_coop_excl_scan(cnt, &chunk);
 			if(si < ns){ found[si] = first; kcnt[si] = o; }          /* found: first entry of the z-mer's occurrence list; kcnt: where its combinations start in the flat order */
 			nflat += chunk;

@@ -19,6 +19,7 @@ SYMBOLS = [
     "wtz_pairs_windows", "wtz_pairs_align", "wtz_fetch_cigars", "wtz_fetch_cigar_text", "wtz_fetch_cigar_text_begin", "wtz_fetch_cigar_text_end", "wtz_cigar_text_device", "wtz_host_alloc", "wtz_host_free", "wtz_get_counters", "wtz_reset_counters",
     "wtz_test_dp", "wtz_extend_batch", "wtz_local_batch", "wtz_kext_batch", "wtz_align_batch", "wtz_global_batch", "wtz_alignx_batch", "wtz_pwtext_batch", "wtz_pool_info", "wtz_pool_failure_kind",
     "wtz_index_count", "wtz_index_counts_fetch", "wtz_index_finish", "wtz_candidate_groups_begin", "wtz_candidate_groups_end", "wtz_candidate_groups_fetch", "wtz_cand_tail_host", "wtz_zindex_build_subset", "wtz_zindex_build_queries", "wtz_upload_reads_ascii", "wtz_fetch_read_bits", "wtz_append_revcomp_views",
+    "wtz_pairs_seed_region", "wtz_hzmaux_batch",
 ]
 
 
@@ -73,6 +74,7 @@ GLOBAL_RESULT = np.dtype([(n, "<i4") for n in ("score", "aln", "mat", "mis", "in
 GLOB_MAXSLOTS = 2047      # band slots of one K-glob wavefront (WTZ_GLOB_MAXSLOTS); wider problems run the wide forms 33 / 255
 ALIGNX_RESULT = np.dtype([(n, "<i4") for n in ("found", "score", "tb", "te", "qb", "qe", "aln", "mat", "mis", "ins", "del", "band")] +
                          [("form_used", "<u4"), ("cigar_len", "<u4"), ("cigar_off", "<u8")])
+HZMAUX_RESULT = np.dtype([(n, "<i4") for n in ("found", "score", "tb", "te", "qb", "qe", "aln", "mat", "mis", "ins", "del")] + [("cigar_len", "<u4"), ("cigar_off", "<u8")])
 PWTEXT_IN = np.dtype([("qb", "<i4"), ("tb", "<i4"), ("cigar_len", "<u4"), ("pad", "<u4"), ("cigar_off", "<u8")])
 PWTEXT_RESULT = np.dtype([("text_off", "<u8"), ("cols", "<u4"), ("pad", "<u4")])
 
@@ -208,6 +210,41 @@ class Context:
         out = np.zeros(q.size, dtype=PAIR_SUMMARY)
         self._chk(self.lib.wtz_pairs_seed(self.h, q.ctypes.data, c.ctypes.data, q.size, out.ctypes.data))
         return out
+
+    def pairs_seed_region(self, q, c, beg, end):
+        """wtz_pairs_seed_region: pairs_seed with one interval [beg, end) of the indexed read q per pair (align_hzmaux's beg / end; needs aux_strand = 1)"""
+        q = np.ascontiguousarray(q, dtype=np.uint32)
+        c = np.ascontiguousarray(c, dtype=np.uint32)
+        beg = np.ascontiguousarray(beg, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        assert q.size == c.size == beg.size == end.size
+        out = np.zeros(q.size, dtype=PAIR_SUMMARY)
+        self.lib.wtz_pairs_seed_region.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        self._chk(self.lib.wtz_pairs_seed_region(self.h, q.ctypes.data, c.ctypes.data, beg.ctypes.data, end.ctypes.data, q.size, out.ctypes.data))
+        return out
+
+    def zindex_build_subset(self, ids):
+        """the z-index of the listed reads only (ascending ids); every other read gets an empty slice"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        self.lib.wtz_zindex_build_subset.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        self._chk(self.lib.wtz_zindex_build_subset(self.h, ids.ctypes.data, ids.size))
+
+    def hzmaux_batch(self, tid, rid, beg, end):
+        """align_hzmaux per (target read, query read, beg, end) in one call (wtz_hzmaux_batch): (records, CIGAR words); the CIGAR of record i is
+        words[cigar_off : cigar_off + cigar_len].  The buffer holds one word per base of every pair, which no CIGAR exceeds."""
+        tid = np.ascontiguousarray(tid, dtype=np.uint32)
+        rid = np.ascontiguousarray(rid, dtype=np.uint32)
+        beg = np.ascontiguousarray(beg, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        assert tid.size == rid.size == beg.size == end.size
+        out = np.zeros(tid.size, dtype=HZMAUX_RESULT)
+        lens = self._keep[2].astype(np.int64)
+        ok = (tid < lens.size) & (rid < lens.size)
+        cap = int(lens[tid[ok]].sum() + lens[rid[ok]].sum()) + 2
+        cig = np.zeros(cap, dtype=np.uint32)
+        self.lib.wtz_hzmaux_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64]
+        self._chk(self.lib.wtz_hzmaux_batch(self.h, tid.ctypes.data, rid.ctypes.data, beg.ctypes.data, end.ctypes.data, tid.size, out.ctypes.data, cig.ctypes.data, cap))
+        return out, cig[:int(out["cigar_len"].sum())].copy()
 
     def pairs_windows(self, summary):
         n = int(summary["nwin"].sum())
