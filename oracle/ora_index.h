@@ -38,6 +38,7 @@ typedef struct {
 	uint64_t *mers;     /* distinct sampled k-mers, ascending */
 	uint64_t *offs;     /* start of the k-mer's run in seeds[] */
 	uint32_t *cnts;     /* run length (0 when filtered) */
+	uint32_t *sat;      /* occurrences, saturating at 0xFFFF (wtzmo.c:276) */
 	uint8_t  *flt;      /* 1: too frequent or singleton */
 	size_t    n_mer;
 	uint32_t *seeds;    /* rd_id<<1|dir, ascending inside each run */
@@ -81,7 +82,7 @@ static int ora_kocc_cmp(const void *pa, const void *pb){
 	} } while(0)
 
 static void ora_kindex_free(ora_kindex_t *ix){
-	free(ix->mers); free(ix->offs); free(ix->cnts); free(ix->flt); free(ix->seeds);
+	free(ix->mers); free(ix->offs); free(ix->cnts); free(ix->sat); free(ix->flt); free(ix->seeds);
 	memset(ix, 0, sizeof(*ix));
 }
 
@@ -106,6 +107,7 @@ static void ora_kindex_build(ora_kindex_t *ix, const ora_store_t *st, uint32_t b
 	ix->mers = (uint64_t*)ora_xrealloc(NULL, n_mer * 8);
 	ix->offs = (uint64_t*)ora_xrealloc(NULL, n_mer * 8);
 	ix->cnts = (uint32_t*)ora_xrealloc(NULL, n_mer * 4);
+	ix->sat  = (uint32_t*)ora_xrealloc(NULL, n_mer * 4);
 	ix->flt  = (uint8_t*) ora_xrealloc(NULL, n_mer);
 	ix->n_mer = n_mer;
 	/* counts saturate at 0xFFFF (wtzmo.c:276) */
@@ -113,7 +115,7 @@ static void ora_kindex_build(ora_kindex_t *ix, const ora_store_t *st, uint32_t b
 	for(size_t i = 0; i < occ.n; ){
 		size_t j = i; while(j < occ.n && occ.a[j].mer == occ.a[i].mer) j++;
 		uint64_t c = j - i; if(c > 0xFFFFu) c = 0xFFFFu;
-		ix->mers[m] = occ.a[i].mer; ix->cnts[m] = (uint32_t)c; ix->offs[m] = i; /* occ offset for now */
+		ix->mers[m] = occ.a[i].mer; ix->cnts[m] = ix->sat[m] = (uint32_t)c; ix->offs[m] = i; /* occ offset for now */
 		ktot += c; m++; i = j;
 	}
 	if(P->max_kmer_freq < 2){      /* wtzmo.c:380-393 */

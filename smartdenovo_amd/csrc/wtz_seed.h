@@ -616,8 +616,8 @@ typedef struct { uint32_t qoff, qlen; } wtz_kq_t;
  * threshold of 150. */
 #define WTZ_CWG_SKETCH 65536u
 /* second level: from how many listed tuples on, and how many units one part of it may hold (the host emulation sets both small so that the CPU suite's little inputs go
- * through the second level and through several parts of it) */
-#ifdef WTZ_EMUL
+ * through the second level and through several parts of it; WTZ_EMUL_DEVICE_THRESHOLDS builds it with the device's values, for inputs sized to cross those) */
+#if defined(WTZ_EMUL) && !defined(WTZ_EMUL_DEVICE_THRESHOLDS)
 #define WTZ_CWG_L2_MIN 48u
 #define WTZ_CWG_L2_PART_UNITS 1024u
 #else

@@ -196,13 +196,91 @@ class Context:
     def zindex_build(self):
         self._chk(self.lib.wtz_zindex_build(self.h))
 
-    def candidates(self, qids):
-        qids = np.ascontiguousarray(qids, dtype=np.uint32)
+    def _cand_rows(self, qids, carry):
+        """rows of ncand + 1 words and their entry counts: zero, or the carried-in (rows, n) of an earlier index part copied"""
         stride = self.params.ncand + 1
         rows = np.zeros((qids.size, stride), dtype=np.uint64)
         n = np.zeros(qids.size, dtype=np.uint32)
+        if carry is not None:
+            rows[:] = np.asarray(carry[0], dtype=np.uint64).reshape(qids.size, stride)
+            n[:] = np.asarray(carry[1], dtype=np.uint32)
+        return rows, n
+
+    def candidates(self, qids, carry=None):
+        """wtz_candidates; carry = the (rows, n) of the same queries from the index parts before this one (-G), so that ncand_io is nonzero on entry"""
+        qids = np.ascontiguousarray(qids, dtype=np.uint32)
+        rows, n = self._cand_rows(qids, carry)
         self._chk(self.lib.wtz_candidates(self.h, qids.ctypes.data, qids.size, rows.ctypes.data, n.ctypes.data))
         return rows, n
+
+    def candidates_begin(self, qids, carry=None):
+        """wtz_candidates_begin: nothing else may be called on the context before candidates_end"""
+        qids = np.ascontiguousarray(qids, dtype=np.uint32)
+        rows, n = self._cand_rows(qids, carry)
+        self._pending = (qids, rows, n)
+        self.lib.wtz_candidates_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.wtz_candidates_begin(self.h, qids.ctypes.data, qids.size, rows.ctypes.data, n.ctypes.data))
+
+    def candidates_end(self):
+        _, rows, n = self._pending
+        self.lib.wtz_candidates_end.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.wtz_candidates_end(self.h, rows.ctypes.data, n.ctypes.data))
+        return rows, n
+
+    def index_count(self, beg=0, end=None):
+        """wtz_index_count + wtz_index_counts_fetch: the shard's distinct sampled k-mers (ascending), their occurrences in it, and n_occ"""
+        nd, no = C.c_uint64(0), C.c_uint64(0)
+        self.lib.wtz_index_count.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        self._chk(self.lib.wtz_index_count(self.h, beg, self.n_reads if end is None else end, C.byref(nd), C.byref(no)))
+        kmers = np.zeros(nd.value, dtype=np.uint64)
+        cnts = np.zeros(nd.value, dtype=np.uint32)
+        self.lib.wtz_index_counts_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.wtz_index_counts_fetch(self.h, kmers.ctypes.data, cnts.ctypes.data))
+        return kmers, cnts, int(no.value)
+
+    def index_finish(self, total_cnt, K):
+        """wtz_index_finish: total_cnt[i] = occurrences of the i-th k-mer of index_count over ALL shards; returns n_kept"""
+        total_cnt = np.ascontiguousarray(total_cnt, dtype=np.uint32)
+        nk = C.c_uint64(0)
+        self.lib.wtz_index_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
+        self._chk(self.lib.wtz_index_finish(self.h, total_cnt.ctypes.data, K, C.byref(nk)))
+        return int(nk.value)
+
+    def candidate_groups(self, qids):
+        """wtz_candidate_groups_begin / _end / _fetch: per query the groups with ol >= -d as (read << 1 | strand) << 32 | ol, in key order"""
+        qids = np.ascontiguousarray(qids, dtype=np.uint32)
+        ng = np.zeros(qids.size, dtype=np.uint32)
+        self.lib.wtz_candidate_groups_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        self.lib.wtz_candidate_groups_end.argtypes = [C.c_void_p, C.c_void_p]
+        self.lib.wtz_candidate_groups_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        self._chk(self.lib.wtz_candidate_groups_begin(self.h, qids.ctypes.data, qids.size))
+        self._chk(self.lib.wtz_candidate_groups_end(self.h, ng.ctypes.data))
+        tot = int(ng.sum(dtype=np.uint64))
+        g = np.zeros(tot, dtype=np.uint64)
+        self._chk(self.lib.wtz_candidate_groups_fetch(self.h, g.ctypes.data, tot))
+        return np.split(g, np.cumsum(ng.astype(np.int64))[:-1]) if qids.size else []
+
+    def cand_tail_host(self, groups, carry=None):
+        """wtz_cand_tail_host: strand merge + candidate heap (wtzmo.c:516-571) over one query's groups; returns (row, n)"""
+        groups = np.ascontiguousarray(groups, dtype=np.uint64)
+        row = np.zeros(self.params.ncand + 1, dtype=np.uint64)
+        hn = C.c_uint32(0)
+        if carry is not None:
+            row[:] = carry[0]; hn.value = int(carry[1])
+        self.lib.wtz_cand_tail_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+        self.lib.wtz_cand_tail_host.restype = None
+        self.lib.wtz_cand_tail_host(groups.ctypes.data, groups.size, self.params.kovl, self.params.ncand, row.ctypes.data, C.byref(hn))
+        return row, int(hn.value)
+
+    def clone(self, pool_bytes=0):
+        """wtz_ctx_clone: a second context on the same device sharing this one's reads and indexes"""
+        other = object.__new__(Context)
+        other.lib, other.params, other.h = self.lib, self.params, C.c_void_p()
+        other.n_reads = self.n_reads
+        other._keep = getattr(self, "_keep", None)
+        self.lib.wtz_ctx_clone.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
+        self._chk(self.lib.wtz_ctx_clone(self.h, pool_bytes, C.byref(other.h)))
+        return other
 
     def pairs_seed(self, q, c):
         q = np.ascontiguousarray(q, dtype=np.uint32)
