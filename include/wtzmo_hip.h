@@ -27,6 +27,7 @@
  *                           the host uploads every read and its reverse complement, smartdenovo_amd/csrc/host/wtgbo_main.c)
  *   wtz_pairs_seed_region <- the same with beg / end: query_single_read_seeds_by_region   hzm_aln.h:117-171, 1690-1693 (wtmsa.c:448-477, wtjnt)
  *   wtz_hzmaux_batch     <- align_hzmaux as one call per batch of (target, read, beg, end)  hzm_aln.h:1684-1775
+ *   wtz_set_window_chaining <- HZM_FAST_WINDOW_KMER_CHAINING: the windows of a scan by the median diagonal or by chaining_hzmps   hzm_aln.h:36, 488, 544 (351-408)
  *
  * Everything returned is integer and bit-exact against `wtzmo -t 1`.  The order-dependent state of
  * the reference (closed pairs, contained-read masking, per-read coverage: wtzmo.c:806-822, 1065-1100,
@@ -209,6 +210,15 @@ int  wtz_pairs_seed(wtz_ctx_t *ctx, const uint32_t *qid, const uint32_t *cid, ui
  * extensions run into the whole indexed read (hzm_aln.h:1714) and tb / te of the alignment may lie outside [beg, end).
  * Needs params.aux_strand = 1 and the zmo engine (params.dot_matrix = 0): WTZ_E_ARG otherwise.  With (0, 0) for every pair it returns what wtz_pairs_seed returns. */
 int  wtz_pairs_seed_region(wtz_ctx_t *ctx, const uint32_t *qid, const uint32_t *cid, const int32_t *beg, const int32_t *end, uint32_t n, wtz_pair_summary_t *out);
+
+/* The reference's process-wide HZM_FAST_WINDOW_KMER_CHAINING (hzm_aln.h:36), per context.  fast = 1, the default: every window of a scan
+ * (potential_paired_kmers_windows) keeps the members within 50 of its median diagonal, ordered by off1 (hzm_aln.h:488-543) - wtzmo, wtgbo.  fast = 0, what wtmsa
+ * and wtcns set at the top of main (wtmsa.c:617, wtcns.c:806): the members of a window are chained by chaining_hzmps (hzm_aln.h:544-561, 351-408) and the chain is
+ * the window - its anchors in chain order, its box from the first and the last anchor, its weight the chain's coverage of the read.  The reference hands the
+ * window's last member over as an exclusive end (hzm_aln.h:545, 360), so that member is never part of the chain; this is kept.  The setting holds for every later
+ * wtz_pairs_seed, wtz_pairs_seed_region and wtz_hzmaux_batch of the context, and wtz_ctx_clone copies it.  fast = 0 needs params.aux_strand = 1 and the zmo engine
+ * (the callers that set it are align_hzmaux's): WTZ_E_ARG otherwise, and the setting stays as it was. */
+int  wtz_set_window_chaining(wtz_ctx_t *ctx, int fast);
 
 /* Chain windows of the last wtz_pairs_seed, packed in (pair, strand) order: sum of nwin[] entries. */
 int  wtz_pairs_windows(wtz_ctx_t *ctx, wtz_winbox_t *wins, uint64_t n_wins);

@@ -62,6 +62,7 @@ struct wtz_ctx {
 	hipStream_t stream_side = 0; hipEvent_t ev_side_fork = 0, ev_side_join = 0;      /* side stream of the fused K-sw3 stage: the items dealt to the 32-bit frame form run on it beside the packed launch (run_stitch_fused) */
 	hipStream_t stream_gap = 0; hipEvent_t ev_gap_fork = 0, ev_gap_join = 0;   /* side stream of K_gap (runs beside the left extensions) */
 #endif
+	int window_chaining = 1;          /* wtz_set_window_chaining: HZM_FAST_WINDOW_KMER_CHAINING of the reference (hzm_aln.h:36); 0 = K_pair_chain */
 	bool shares_indexes = false;      /* clone: reads / k-mer table / z-index belong to the parent context */
 	void *kpark_p[2] = {NULL, NULL}; size_t kpark_b[2] = {0, 0}, klive_b[2] = {0, 0};      /* k-mer table [0] / seed list [1]: buffer parked for the next build, size of the live one (0: not from kalloc) */
 	wtz_arena arena;          /* transient device buffers of the API call in progress */
@@ -327,7 +328,7 @@ extern "C" int wtz_ctx_clone(wtz_ctx_t *p, uint64_t pool_bytes, wtz_ctx_t **out)
 	wtz_ctx_t *c = NULL;
 	int rc = wtz_ctx_create(p->device, &p->P, pool_bytes ? pool_bytes : p->pool_bytes, &c);
 	if(rc) return rc;
-	c->shares_indexes = true;
+	c->shares_indexes = true; c->window_chaining = p->window_chaining;
 	c->bits = p->bits; c->n_words = p->n_words; c->rdoff = p->rdoff; c->rdlen = p->rdlen; c->n_reads = p->n_reads; c->h_rdlen = p->h_rdlen;
 	c->ktab = p->ktab; c->kmask = p->kmask; c->kseeds = p->kseeds; c->n_kocc = p->n_kocc;
 	c->idx_beg = p->idx_beg; c->idx_end = p->idx_end; c->idx_len_sorted = p->idx_len_sorted;

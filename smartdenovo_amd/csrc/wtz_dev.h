@@ -80,6 +80,7 @@ template<typename TAG> struct wtz_occ { static constexpr int waves = 1; };
 template<> struct wtz_occ<K_winalign> { static constexpr int waves = WTZ_OCC_WINALIGN; };
 template<> struct wtz_occ<K_pair> { static constexpr int waves = WTZ_OCC_PAIR; };
 template<> struct wtz_occ<K_pair_region> { static constexpr int waves = WTZ_OCC_PAIR; };      /* K_pair's body + the run cut of the interval form */
+template<> struct wtz_occ<K_pair_chain> { static constexpr int waves = WTZ_OCC_PAIR; };       /* K_pair_region's body with chaining_hzmps for the per-window block of the scans */
 template<> struct wtz_occ<K_pair_dm> { static constexpr int waves = WTZ_OCC_PAIR_DM; };
 template<> struct wtz_occ<K_pair_zbig> { static constexpr int waves = 2; };      /* both scan bodies (168 VGPRs + spills at three waves); a handful of pairs per launch, each a long dependent chain */
 template<> struct wtz_occ<K_gap> { static constexpr int waves = WTZ_OCC_GAP; };

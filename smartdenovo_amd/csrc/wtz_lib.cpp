@@ -71,6 +71,7 @@ struct K_pair_dm;
 struct K_pair_zbig;
 struct K_pair_big;
 struct K_pair_region;
+struct K_pair_chain;
 struct K_refine;
 struct K_pack_ascii;
 struct K_pack_fix;

@@ -1,6 +1,7 @@
 /*
  * wtz_lib_pairs.h — the per-batch pair stages in front of the alignment: wtz_batch_begin, wtz_pairs_seed (K_pair and the launches that finish what it
- * leaves), wtz_pairs_seed_region (the same with one interval of the indexed read per pair: K_pair_region) and wtz_pairs_windows.  Included by wtz_lib.cpp.
+ * leaves), wtz_pairs_seed_region (the same with one interval of the indexed read per pair: K_pair_region), wtz_set_window_chaining (both through K_pair_chain)
+ * and wtz_pairs_windows.  Included by wtz_lib.cpp.
  */
 #ifndef WTZ_PAIR_DM_LDS_TIER2
 #define WTZ_PAIR_DM_LDS_TIER2 49152u
@@ -41,7 +42,8 @@ static void wtz_crumbs_dump(int sig){
 #endif
 
 /* wtz_pairs_seed (beg == NULL) and wtz_pairs_seed_region (one interval [beg[i], end[i]) of read qid[i] per pair, defaults applied by the caller): the
- * two differ in the first launch only, K_pair or K_pair_region */
+ * two differ in the first launch only, K_pair or K_pair_region.  After wtz_set_window_chaining(ctx, 0) that launch is K_pair_chain for both: the whole form is
+ * the interval [0, length of the indexed read), which cuts nothing (hzm_aln.h:1690-1691) */
 static int pairs_seed_run(wtz_ctx_t *c, const char *who, const uint32_t *qid, const uint32_t *cid, const int32_t *beg, const int32_t *end, uint32_t n, wtz_pair_summary_t *out){
 	if(!c || !c->zs[0].have || (n && (!qid || !cid || !out))) return wtz_fail(WTZ_E_ARG, "z-index not built / null argument");
 	CTX_ENTER(c);
@@ -52,17 +54,18 @@ static int pairs_seed_run(wtz_ctx_t *c, const char *who, const uint32_t *qid, co
 	CHK(reserve_pairs(c, n));
 	CHK(dev_h2d(c->d_qid, qid, (size_t)n * 4)); CHK(dev_h2d(c->d_cid, cid, (size_t)n * 4));
 	int32_t *d_beg = NULL, *d_end = NULL;
-	if(beg){
+	const bool chain = c->window_chaining == 0;
+	if(beg || chain){
 		/* the defaults of hzm_aln.h:1690-1691: beg < 0 -> 0, end <= 0 -> the length of the indexed read; an end behind the read stays as it is (it excludes nothing) */
 		std::vector<int32_t> b(n), e(n);
-		for(uint32_t i = 0; i < n; i++){ b[i] = beg[i] < 0 ? 0 : beg[i]; e[i] = end[i] <= 0 ? (int32_t)c->h_rdlen[qid[i]] : end[i]; }
+		for(uint32_t i = 0; i < n; i++){ b[i] = (!beg || beg[i] < 0) ? 0 : beg[i]; e[i] = (!beg || end[i] <= 0) ? (int32_t)c->h_rdlen[qid[i]] : end[i]; }
 		CHK(dev_alloc((void**)&d_beg, (size_t)n * 4)); CHK(dev_h2d(d_beg, b.data(), (size_t)n * 4));
 		CHK(dev_alloc((void**)&d_end, (size_t)n * 4)); CHK(dev_h2d(d_end, e.data(), (size_t)n * 4));
 	}
 	const wtz_env_t V = ctx_env(c); const uint32_t *dq = c->d_qid, *dc = c->d_cid; wtz_pairres_t *dr = c->d_pairres;
 	wtz_timer tm; tm.start();
 	wtz_timer t1; t1.start();
-	const char *kname = beg ? "K_pair_region" : "K_pair";
+	const char *kname = chain ? "K_pair_chain" : beg ? "K_pair_region" : "K_pair";
 	STAGE(c, kname);
 #if defined(WTZ_DEBUG_CRUMBS) && !defined(WTZ_EMUL)
 	unsigned int *h_crumbs = NULL;
@@ -102,11 +105,14 @@ static int pairs_seed_run(wtz_ctx_t *c, const char *who, const uint32_t *qid, co
 #endif
 	const uint64_t n64 = n - nh; const uint64_t nh64 = nh;
 #ifdef WTZ_EMUL
-	if(beg) CHK(wtz_launch_coop<K_pair_region>(n, [=] WTZ_LAMBDA (uint64_t b){ wtz_task_pair<-1, true, true>((uint32_t)b, V, dq, dc, dr, d_beg, d_end); }, WTZ_PAIR_LDS_BYTES));
+	if(chain) CHK(wtz_launch_coop<K_pair_chain>(n, [=] WTZ_LAMBDA (uint64_t b){ wtz_task_pair<-1, true, true, true>((uint32_t)b, V, dq, dc, dr, d_beg, d_end); }, WTZ_PAIR_LDS_BYTES));
+	else if(beg) CHK(wtz_launch_coop<K_pair_region>(n, [=] WTZ_LAMBDA (uint64_t b){ wtz_task_pair<-1, true, true>((uint32_t)b, V, dq, dc, dr, d_beg, d_end); }, WTZ_PAIR_LDS_BYTES));
 	else
 	CHK(wtz_launch_coop<K_pair>(n, [=] WTZ_LAMBDA (uint64_t b){ (void)xg; (void)n64; (void)nh64; (void)d_ord; wtz_task_pair<-1>((uint32_t)b, V, dq, dc, dr); }, c->P.dot_matrix ? WTZ_PAIR_DM_LDS_BYTES : WTZ_PAIR_LDS_BYTES));
 #else
-	if(beg){
+	if(chain){
+		CHK(wtz_launch_coop<K_pair_chain>(n, [=] WTZ_LAMBDA (uint64_t b){ wtz_task_pair<0, true, true, true>((uint32_t)b, V, dq, dc, dr, d_beg, d_end); }, WTZ_PAIR_LDS_BYTES));
+	} else if(beg){
 		/* the pairs in the caller's order: the pairs of a layout share ONE query table, the backbone's, so there is nothing for the XCD mapping of K_pair to keep together */
 		CHK(wtz_launch_coop<K_pair_region>(n, [=] WTZ_LAMBDA (uint64_t b){ wtz_task_pair<0, true, true>((uint32_t)b, V, dq, dc, dr, d_beg, d_end); }, WTZ_PAIR_LDS_BYTES));
 	} else if(c->P.dot_matrix){
@@ -218,6 +224,14 @@ extern "C" int wtz_pairs_seed_region(wtz_ctx_t *c, const uint32_t *qid, const ui
 	CHK(region_args(c, "wtz_pairs_seed_region"));
 	if(n && (!beg || !end)) return wtz_fail(WTZ_E_ARG, "null argument");
 	return pairs_seed_run(c, "wtz_pairs_seed_region", qid, cid, beg, end, n, out);
+}
+
+/* HZM_FAST_WINDOW_KMER_CHAINING of the reference (hzm_aln.h:36), per context: 1 = the median-diagonal filter of hzm_aln.h:488-543, 0 = chaining_hzmps, hzm_aln.h:544-561 */
+extern "C" int wtz_set_window_chaining(wtz_ctx_t *c, int fast){
+	if(!c) return wtz_fail(WTZ_E_ARG, "null context");
+	if(!fast) CHK(region_args(c, "wtz_set_window_chaining(0)"));
+	c->window_chaining = fast ? 1 : 0;
+	return WTZ_OK;
 }
 
 extern "C" int wtz_pairs_windows(wtz_ctx_t *c, wtz_winbox_t *wins, uint64_t n_wins){

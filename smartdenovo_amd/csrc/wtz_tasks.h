@@ -62,7 +62,9 @@ __device__ unsigned int *wtz_crumbs = NULL;
 /* REGION: align_hzmaux with beg / end (wtmsa's call, wtmsa.c:448-477): the z-mer matches of pair t are those of the interval [reg_beg[t], reg_end[t]) of the
  * query, the indexed side (wtz_zmatch_coop<true>); the host has applied the defaults of hzm_aln.h:1690-1691.  Everything behind the matches is blind to the
  * interval, as in the reference (hzm_aln.h:1696-1718).  A launch of its own (wtz_pairs_seed_region): the form without an interval does not carry the test. */
-template<int ENGINE = -1, bool ZBIG = true, bool REGION = false>
+/* CHAIN: the windows of a scan by chaining_hzmps (HZM_FAST_WINDOW_KMER_CHAINING = 0, as wtmsa and wtcns set it: wtz_set_window_chaining, wtz_window.h), a launch of
+ * its own (K_pair_chain): the other forms do not carry the branch. */
+template<int ENGINE = -1, bool ZBIG = true, bool REGION = false, bool CHAIN = false>
 WTZ_HD void wtz_task_pair(uint32_t t, const wtz_env_t &V, const uint32_t *qid, const uint32_t *cid, wtz_pairres_t *res, const int32_t *reg_beg = NULL, const int32_t *reg_end = NULL){
 	const wtz_params_t *P = V.P;
 	const int32_t rtb = REGION ? reg_beg[t] : 0, rte = REGION ? reg_end[t] : 0;
@@ -157,9 +159,9 @@ WTZ_HD void wtz_task_pair(uint32_t t, const wtz_env_t &V, const uint32_t *qid, c
 		WTZ_CRUMB(t, (6 + dir) | (n << 8));
 		const unsigned long long ptm = WTZ_PROF_T(); (void)ptm;
 #ifdef WTZ_MERGE_SCALAR
-		const uint32_t nw = wtz_merge_windows_coop<ZBIG>(hits, n, dir, wins, anchors, sc, P->zsize, P->kwin, P->kstep, P->zovl);
+		const uint32_t nw = wtz_merge_windows_coop<ZBIG, CHAIN>(hits, n, dir, wins, anchors, sc, P->zsize, P->kwin, P->kstep, P->zovl);
 #else
-		const uint32_t nw = wtz_merge_windows_wave<ZBIG>(hits, n, dir, wins, anchors, sc, P->zsize, P->kwin, P->kstep, P->zovl);
+		const uint32_t nw = wtz_merge_windows_wave<ZBIG, CHAIN>(hits, n, dir, wins, anchors, sc, P->zsize, P->kwin, P->kstep, P->zovl);
 #endif
 		WTZ_PROF_ADD(63, ptm);      /* profiler: 63 = merge loop incl. its scans, 62 = chain + compaction */
 		if(!ZBIG && sc.need_big){          /* a range that does not fit the LDS slice: the whole pair again in the launch with the pool-workspace body */

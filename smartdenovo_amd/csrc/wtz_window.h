@@ -339,7 +339,7 @@ WTZ_HD void wtz_hitcur_get(wtz_hitcur_t &c, const wtz_zhit_t *rs, uint32_t lim, 
 #ifndef WTZ_SCAN_FN
 #define WTZ_SCAN_FN WTZ_HD
 #endif
-template<bool K_LDS>
+template<bool K_LDS, bool CHAIN = false>
 WTZ_SCAN_REST_FN uint32_t wtz_scan_windows_rest(const wtz_zhit_t *rs, uint32_t dir, uint32_t beg, uint32_t end, int32_t bound,
 		wtz_vec<wtz_win_t> &wins, wtz_vec<wtz_zhit_t> &anchors, const wtz_winscratch_t &sc, uint32_t zsize, uint32_t kwin, uint32_t zovl, int32_t *max_e0, uint32_t n, unsigned long long pw0, uint64_t *KB){
 	const uint32_t lane = WTZ_LANE;
@@ -408,6 +408,7 @@ retry_scan:
 	if(had_tie) WTZ_PROF_CNT(26, 1000);
 	}
 	WTZ_PROF_ADD(17, pw1);
+	if constexpr(CHAIN){ if(had_tie && !exact){ WTZ_PROF_CNT(28, 1000); exact = true; goto retry_scan; } }      /* the chain form observes the order inside a tie group anywhere in a window: the reference's swap sequence at once */
 	const unsigned long long pw2 = WTZ_PROF_T(); (void)pw2;
 	wtz_zhit_t *S = (wtz_zhit_t*)(K + np);
 	for(uint32_t x = lane; x < n; x += WTZ_NLANES) S[x] = rs[(uint32_t)K[x]];
@@ -475,6 +476,99 @@ retry_scan:
 	 *  - anchors copied one per lane; the covered length is a sum of per-member terms that depend on the member before only (len1, or end - previous end), the box
 	 *    is four min / max reductions. ---- */
 	if(n2_all == 0xFFFFFFFFu){ WTZ_PROF_CNT(28, 1000); exact = true; goto retry_scan; }
+	if constexpr(CHAIN){
+	/* ---- the windows of the chain form (HZM_FAST_WINDOW_KMER_CHAINING = 0: hzm_aln.h:544-561 with chaining_hzmps, hzm_aln.h:351-408).  The nodes are the matches
+	 * [ws.b, ws.e) in S order - the reference hands ws.e over as an EXCLUSIVE end (hzm_aln.h:545, 360), so the window's last member is not a node - with
+	 * (weight, bt) per node in K (one 64-bit word each; the off2 keys and EP are dead).  Node i is final when the uniform outer loop reaches it (a predecessor has a
+	 * smaller index); the lanes take its successors j = i + 1 + lane, + 64, ... up to the first j with off2[j] > off2[i] + W (a break; S ascends in off2: one
+	 * ballot) and each updates its own node.  Both comparisons are strict (hzm_aln.h:369, 383): the first maximum ends the chain, the first best predecessor stays.
+	 * The weight is the reference's `int + int - int * 0.5f` in float, truncated toward zero on assignment (hzm_aln.h:380-382).  Chain members have ascending
+	 * node indexes, so the back-walk (lane 0) only marks them and the anchors are their compaction in S order: ascending in off2 and off1, not re-sorted. ---- */
+	const int32_t CW = (int32_t)(kwin / 8 > 64u ? kwin / 8 : 64u);
+	int32_t *NW = (int32_t*)K;
+	int32_t last_end1 = 0; uint32_t last_ovl = 0;
+	for(uint32_t wi = 0; wi < n2_all; wi++){
+		uint32_t size = 0, wb = 0, we = 0;
+		if(lane == 0){ size = anchors.n; wb = sc.wb[wi]; we = sc.we[wi]; }
+		size = wtz_coop_bcast32(size); wb = wtz_coop_bcast32(wb); we = wtz_coop_bcast32(we);
+		const uint32_t m = we - wb;
+		if(m == 0) continue;                                    /* hzm_aln.h:546: nothing pushed */
+		WTZ_WAVE_SYNC();
+		for(uint32_t x = lane; x < m; x += WTZ_NLANES){ NW[2 * x] = (int32_t)ZH_LEN2(S[wb + x]); NW[2 * x + 1] = -1; }
+		WTZ_WAVE_SYNC();
+		int32_t mw = -1000000, bt = -1;
+		for(uint32_t i = 0; i < m; i++){
+			const wtz_zhit_t r1 = S[wb + i];
+			const int32_t w1 = (int32_t)wtz_coop_bcast32((uint32_t)NW[2 * i]);
+			const int32_t a1 = (int32_t)wtz_coop_bcast32(ZH_OFF1(r1)), b1 = (int32_t)wtz_coop_bcast32(ZH_OFF2(r1)), e1 = b1 + (int32_t)wtz_coop_bcast32(ZH_LEN2(r1));
+			if(w1 > mw){ mw = w1; bt = (int32_t)i; }
+			for(uint32_t j0 = i + 1; j0 < m; j0 += WTZ_NLANES){
+				const uint32_t j = j0 + lane; const bool in = j < m;
+				int32_t a2 = 0, b2 = 0, l2 = 0;
+				if(in){ const wtz_zhit_t r2 = S[wb + j]; a2 = (int32_t)ZH_OFF1(r2); b2 = (int32_t)ZH_OFF2(r2); l2 = (int32_t)ZH_LEN2(r2); }
+				const unsigned long long far = wtz_coop_ballot(in && b2 > b1 + CW);
+				const uint32_t stop_at = far ? (uint32_t)__builtin_ctzll(far) : WTZ_NLANES;
+				if(in && lane < stop_at && b2 > b1 && a2 > a1){
+					const int32_t d1 = a2 - a1, d2 = b2 - b1, band = d1 < d2 ? d2 - d1 : d1 - d2;      /* num_diff of two int differences (list.h:36) */
+					int32_t wt = (b2 + l2) - e1;
+					if(wt > l2) wt = l2;
+					wt = (int32_t)((float)(wt + w1) - (float)band * 0.5f);
+					if(NW[2 * j] < wt){ NW[2 * j] = wt; NW[2 * j + 1] = (int32_t)i; }
+				}
+				if(far) break;
+			}
+			WTZ_WAVE_SYNC();                                     /* the updates of this step are visible to the uniform reads of the next */
+		}
+		uint32_t cnt = 0;
+		if(lane == 0) for(int32_t b = bt; b >= 0; cnt++){ const int32_t nb = NW[2 * b + 1]; NW[2 * b + 1] = -2; b = nb; }      /* at most m steps: bt < its node */
+		cnt = wtz_coop_bcast32(cnt);
+		WTZ_WAVE_SYNC();
+		if(cnt == 0) continue;
+		uint32_t stop = 0; uint64_t abase = 0;
+		if(lane == 0){ if(!anchors.reserve(size + cnt)) stop = 1; else abase = (uint64_t)(uintptr_t)anchors.a; }
+		if(wtz_coop_bcast32(stop)) break;
+		abase = wtz_coop_bcast64(abase);
+		wtz_zhit_t *A = (wtz_zhit_t*)(uintptr_t)abase + size;
+		uint32_t at = 0;
+		for(uint32_t c0 = 0; c0 < m; c0 += WTZ_NLANES){
+			const uint32_t x = c0 + lane;
+			const bool keep = x < m && NW[2 * x + 1] == -2;
+			uint32_t tot; const uint32_t pos = wtz_coop_rank(keep, &tot);
+			if(keep) A[at + pos] = S[wb + x];
+			at += tot;
+		}
+		WTZ_WAVE_SYNC();
+		uint32_t ol = 0;                                        /* the chain's off2 coverage (hzm_aln.h:393-399), modulo 2^32 like the int it is returned in */
+		for(uint32_t c0 = 0; c0 < cnt; c0 += WTZ_NLANES){
+			const uint32_t k = c0 + lane; uint32_t add = 0;
+			if(k < cnt){
+				const wtz_zhit_t p = A[k];
+				uint32_t lst = 0; if(k){ const wtz_zhit_t q = A[k - 1]; lst = ZH_OFF2(q) + ZH_LEN2(q); }
+				add = (ZH_OFF2(p) >= lst) ? ZH_LEN2(p) : ZH_OFF2(p) + ZH_LEN2(p) - lst;
+			}
+			uint32_t tot; (void)wtz_coop_excl_scan(add, &tot); ol += tot;
+		}
+		const wtz_zhit_t pf = A[0], pl = A[cnt - 1];          /* the box: the first anchor's begins, the last anchor's ends (hzm_aln.h:552-558) */
+		const uint32_t b0 = wtz_coop_bcast32(ZH_OFF1(pf)), b1 = wtz_coop_bcast32(ZH_OFF2(pf));
+		const uint32_t e0 = wtz_coop_bcast32(ZH_OFF1(pl) + ZH_LEN1(pl)), e1 = wtz_coop_bcast32(ZH_OFF2(pl) + ZH_LEN2(pl));
+		if(ol * 2 < zovl) continue;
+		if(ret && ((int32_t)e1 <= (int32_t)((uint32_t)last_end1 + kwin / 3) && ol <= last_ovl)) continue;
+		if(lane == 0){
+			wtz_win_t w;
+			w.pb2 = 0; w.closed = 0; w.dir = (uint8_t)dir; w.pad = 0;
+			w.beg[0] = (int32_t)b0; w.beg[1] = (int32_t)b1; w.end[0] = (int32_t)e0; w.end[1] = (int32_t)e1;
+			anchors.n = size + cnt;
+			w.anchors[0] = size; w.anchors[1] = anchors.n;
+			w.ovl = WTZ_OVL29(ol);
+			if(!wins.push(w)) stop = 1;
+		}
+		if(wtz_coop_bcast32(stop)) break;
+		ret++;
+		last_end1 = (int32_t)e1; last_ovl = WTZ_OVL29(ol);
+		if(me0 < (int32_t)e0) me0 = (int32_t)e0;
+		WTZ_WAVE_SYNC();
+	}
+	} else {
 	int32_t last_end1 = 0; uint32_t last_ovl = 0;
 	for(uint32_t wi = 0; wi < n2_all; wi++){
 		uint32_t size = 0, cnt = 0, wb = 0, we = 0;
@@ -591,6 +685,7 @@ retry_scan:
 		if(me0 < (int32_t)e0) me0 = (int32_t)e0;
 		WTZ_WAVE_SYNC();
 	}
+	}
 	WTZ_PROF_ADD(20, pw4);
 	WTZ_WAVE_SYNC();
 	*max_e0 = (int32_t)wtz_coop_bcast32((uint32_t)me0);
@@ -603,8 +698,13 @@ WTZ_DN uint32_t wtz_scan_windows_rest_pool(const wtz_zhit_t *rs, uint32_t dir, u
 		wtz_vec<wtz_win_t> &wins, wtz_vec<wtz_zhit_t> &anchors, const wtz_winscratch_t &sc, uint32_t zsize, uint32_t kwin, uint32_t zovl, int32_t *max_e0, uint32_t n, unsigned long long pw0, uint64_t *KB){
 	return wtz_scan_windows_rest<false>(rs, dir, beg, end, bound, wins, anchors, sc, zsize, kwin, zovl, max_e0, n, pw0, KB);
 }
+/* ... and its chain form (K_pair_chain) */
+WTZ_DN uint32_t wtz_scan_windows_rest_pool_chain(const wtz_zhit_t *rs, uint32_t dir, uint32_t beg, uint32_t end, int32_t bound,
+		wtz_vec<wtz_win_t> &wins, wtz_vec<wtz_zhit_t> &anchors, const wtz_winscratch_t &sc, uint32_t zsize, uint32_t kwin, uint32_t zovl, int32_t *max_e0, uint32_t n, unsigned long long pw0, uint64_t *KB){
+	return wtz_scan_windows_rest<false, true>(rs, dir, beg, end, bound, wins, anchors, sc, zsize, kwin, zovl, max_e0, n, pw0, KB);
+}
 
-template<bool ZBIG>
+template<bool ZBIG, bool CHAIN = false>
 WTZ_SCAN_FN uint32_t wtz_scan_windows_coop(const wtz_zhit_t *rs, uint32_t dir, uint32_t beg, uint32_t end, int32_t bound,
 		wtz_vec<wtz_win_t> &wins, wtz_vec<wtz_zhit_t> &anchors, const wtz_winscratch_t &sc, uint32_t zsize, uint32_t kwin, uint32_t zovl, int32_t *max_e0){
 	const uint32_t lane = WTZ_LANE;
@@ -759,7 +859,8 @@ WTZ_SCAN_FN uint32_t wtz_scan_windows_coop(const wtz_zhit_t *rs, uint32_t dir, u
 					m += tot;
 				}
 				if constexpr(ZBIG){       /* a real call: its results come back in vector registers - say again that they are uniform */
-					const uint32_t r = wtz_scan_windows_rest_pool(rs, dir, beg, end, bound, wins, anchors, sc, zsize, kwin, zovl, max_e0, n, pw0, KB);
+					const uint32_t r = CHAIN ? wtz_scan_windows_rest_pool_chain(rs, dir, beg, end, bound, wins, anchors, sc, zsize, kwin, zovl, max_e0, n, pw0, KB)
+					                         : wtz_scan_windows_rest_pool(rs, dir, beg, end, bound, wins, anchors, sc, zsize, kwin, zovl, max_e0, n, pw0, KB);
 					*max_e0 = (int32_t)wtz_coop_bcast32((uint32_t)*max_e0);
 					return wtz_coop_bcast32(r);
 				}
@@ -770,10 +871,10 @@ WTZ_SCAN_FN uint32_t wtz_scan_windows_coop(const wtz_zhit_t *rs, uint32_t dir, u
 			}
 		}
 	}
-	return wtz_scan_windows_rest<true>(rs, dir, beg, end, bound, wins, anchors, sc, zsize, kwin, zovl, max_e0, n, pw0, NULL);
+	return wtz_scan_windows_rest<true, CHAIN>(rs, dir, beg, end, bound, wins, anchors, sc, zsize, kwin, zovl, max_e0, n, pw0, NULL);
 }
 
-template<bool ZBIG>
+template<bool ZBIG, bool CHAIN = false>
 WTZ_HD uint32_t wtz_merge_windows_coop(const wtz_zhit_t *rs, uint32_t n_rs, uint32_t dir, wtz_vec<wtz_win_t> &wins, wtz_vec<wtz_zhit_t> &anchors,
 		const wtz_winscratch_t &sc, uint32_t zsize, uint32_t kwin, uint32_t kstep, uint32_t zovl){
 	/* every value this loop branches on is the same in all lanes - say so (v_readfirstlane): without it the compiler keeps the cursors in vector registers and
@@ -799,7 +900,7 @@ WTZ_HD uint32_t wtz_merge_windows_coop(const wtz_zhit_t *rs, uint32_t n_rs, uint
 		if(p_off1 > p0_off1 + kwin){
 			if(ol >= zovl){
 				int32_t me0 = 0;
-				n = wtz_scan_windows_coop<ZBIG>(rs, dir, j, i, (int32_t)wlst, wins, anchors, sc, zsize, kwin, zovl, &me0);
+				n = wtz_scan_windows_coop<ZBIG, CHAIN>(rs, dir, j, i, (int32_t)wlst, wins, anchors, sc, zsize, kwin, zovl, &me0);
 				if(!ZBIG && sc.need_big) return 0;
 				if(n){
 					if((int32_t)wlst < me0 + 20) wlst = (uint32_t)(me0 + 20);
@@ -889,7 +990,7 @@ WTZ_HD void wtz_merge_prepare(const wtz_zhit_t *rs, uint32_t n_rs, const wtz_win
 	WTZ_WAVE_SYNC();
 }
 
-template<bool ZBIG>
+template<bool ZBIG, bool CHAIN = false>
 WTZ_HD uint32_t wtz_merge_windows_wave(const wtz_zhit_t *rs, uint32_t n_rs, uint32_t dir, wtz_vec<wtz_win_t> &wins, wtz_vec<wtz_zhit_t> &anchors,
 		const wtz_winscratch_t &sc, uint32_t zsize, uint32_t kwin, uint32_t kstep, uint32_t zovl){
 	n_rs = wtz_coop_bcast32(n_rs); dir = wtz_coop_bcast32(dir); zsize = wtz_coop_bcast32(zsize); kwin = wtz_coop_bcast32(kwin); kstep = wtz_coop_bcast32(kstep); zovl = wtz_coop_bcast32(zovl);
@@ -934,7 +1035,7 @@ WTZ_HD uint32_t wtz_merge_windows_wave(const wtz_zhit_t *rs, uint32_t n_rs, uint
 		bool taken = false;
 		if(ol >= zovl){
 			int32_t me0 = 0;
-			const uint32_t n = wtz_scan_windows_coop<ZBIG>(rs, dir, j, it, (int32_t)wlst, wins, anchors, sc, zsize, kwin, zovl, &me0);
+			const uint32_t n = wtz_scan_windows_coop<ZBIG, CHAIN>(rs, dir, j, it, (int32_t)wlst, wins, anchors, sc, zsize, kwin, zovl, &me0);
 			if(!ZBIG && sc.need_big) return 0;
 			if(n){
 				if((int32_t)wlst < me0 + 20) wlst = (uint32_t)(me0 + 20);
@@ -963,7 +1064,7 @@ WTZ_HD uint32_t wtz_merge_windows_wave(const wtz_zhit_t *rs, uint32_t n_rs, uint
 	/* the sentinel behind the last match (hzm_aln.h:589): one more scan when the window has enough in it; nothing after it is observable */
 	if(SENT_OFF > wtz_coop_bcast32(ZH_OFF1(rs[j])) + kwin && ol >= zovl){
 		int32_t me0 = 0;
-		const uint32_t n = wtz_scan_windows_coop<ZBIG>(rs, dir, j, n_rs, (int32_t)wlst, wins, anchors, sc, zsize, kwin, zovl, &me0);
+		const uint32_t n = wtz_scan_windows_coop<ZBIG, CHAIN>(rs, dir, j, n_rs, (int32_t)wlst, wins, anchors, sc, zsize, kwin, zovl, &me0);
 		if(!ZBIG && sc.need_big) return 0;
 		ret += n;
 	}
