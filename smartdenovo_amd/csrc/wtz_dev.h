@@ -82,7 +82,6 @@ template<> struct wtz_occ<K_pair> { static constexpr int waves = WTZ_OCC_PAIR; }
 template<> struct wtz_occ<K_pair_region> { static constexpr int waves = WTZ_OCC_PAIR; };      /* K_pair's body + the run cut of the interval form */
 template<> struct wtz_occ<K_pair_chain> { static constexpr int waves = WTZ_OCC_PAIR; };       /* K_pair_region's body with chaining_hzmps for the per-window block of the scans */
 template<> struct wtz_occ<K_pair_dm> { static constexpr int waves = WTZ_OCC_PAIR_DM; };
-template<> struct wtz_occ<K_pair_zbig> { static constexpr int waves = 2; };      /* both scan bodies (168 VGPRs + spills at three waves); a handful of pairs per launch, each a long dependent chain */
 template<> struct wtz_occ<K_gap> { static constexpr int waves = WTZ_OCC_GAP; };
 /* lane-per-problem K-sw1 (wtz_sw_lane.h): the band lives in 2 x (NC + 1) VGPRs */
 #ifndef WTZ_OCC_LDP

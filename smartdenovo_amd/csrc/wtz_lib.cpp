@@ -68,7 +68,6 @@ struct K_pack_cigars;
 struct K_pack_windows;
 struct K_pair;
 struct K_pair_dm;
-struct K_pair_zbig;
 struct K_pair_big;
 struct K_pair_region;
 struct K_pair_chain;

@@ -26,20 +26,29 @@ extern "C" int wtz_batch_begin(wtz_ctx_t *c){
 	return pool_reset(c);
 }
 
-#if defined(WTZ_DEBUG_CRUMBS) && !defined(WTZ_EMUL)
-#include <signal.h>
-#include <unistd.h>
-static unsigned int *g_crumbs = NULL; static uint32_t g_crumbs_n = 0; static const uint32_t *g_crumbs_q = NULL, *g_crumbs_c = NULL;
-static void wtz_crumbs_dump(int sig){
-	unsigned hist[256]; memset(hist, 0, sizeof hist); unsigned shown = 0;
-	for(uint32_t i = 0; i < g_crumbs_n; i++) hist[g_crumbs[i] & 0xFF]++;
-	fprintf(stderr, "[crumbs] signal %d, %u pairs; tasks per last point:", sig, g_crumbs_n);
-	for(int k = 0; k < 256; k++) if(hist[k]) fprintf(stderr, " %d:%u", k, hist[k]);
-	fprintf(stderr, "\n");
-	for(uint32_t i = 0; i < g_crumbs_n && shown < 16; i++) if((g_crumbs[i] & 0xFF) != 0xFF && (g_crumbs[i] & 0xFF) != 0){ fprintf(stderr, "[crumbs]   pair %u (q %u, c %u): point %u, hits %u\n", i, g_crumbs_q[i], g_crumbs_c[i], g_crumbs[i] & 0xFF, g_crumbs[i] >> 8); shown++; }
-	fflush(stderr); _exit(86);
-}
+/* The heavy-first list of wtz_pair_order (wtz_tasks.h): the n / 32 pairs with the largest len(q) * len(c), largest first, then the others in the plan order, as a
+ * device array; *nh = how many head it.  Fewer than 8 of them, or the switch off: no list (*d_ord = NULL, *nh = 0).  WTZ_PAIR_HEAVY_FIRST=0 / 1 overrides the
+ * engine default (dmo on; zmo off: its launches were measured full to the end).  The host emulation runs its pairs in the caller's order. */
+static int pairs_heavy_first(wtz_ctx_t *c, const uint32_t *qid, const uint32_t *cid, uint32_t n, const uint32_t **d_ord, uint32_t *nh){
+	*d_ord = NULL; *nh = 0;
+#ifndef WTZ_EMUL
+	if(!(c->sw.heavy_first >= 0 ? c->sw.heavy_first != 0 : c->P.dot_matrix != 0) || n / 32u < 8u) return WTZ_OK;
+	const uint32_t k = n / 32u;
+	std::vector<uint64_t> key(n); std::vector<uint32_t> ord(n), hv(n);
+	for(uint32_t i = 0; i < n; i++){ key[i] = (uint64_t)c->h_rdlen[qid[i]] * c->h_rdlen[cid[i]]; hv[i] = i; }
+	const auto heavier = [&](uint32_t a, uint32_t b){ return key[a] != key[b] ? key[a] > key[b] : a < b; };
+	std::nth_element(hv.begin(), hv.begin() + k, hv.end(), heavier);
+	std::sort(hv.begin(), hv.begin() + k, heavier);
+	std::vector<uint8_t> heavy(n, 0);
+	for(uint32_t i = 0; i < k; i++){ ord[i] = hv[i]; heavy[hv[i]] = 1; }
+	uint32_t w = k; for(uint32_t i = 0; i < n; i++) if(!heavy[i]) ord[w++] = i;
+	uint32_t *dd = NULL; CHK(dev_alloc((void**)&dd, (size_t)n * 4)); CHK(dev_h2d(dd, ord.data(), (size_t)n * 4));
+	*d_ord = dd; *nh = k;
+#else
+	(void)c; (void)qid; (void)cid; (void)n;
 #endif
+	return WTZ_OK;
+}
 
 /* wtz_pairs_seed (beg == NULL) and wtz_pairs_seed_region (one interval [beg[i], end[i]) of read qid[i] per pair, defaults applied by the caller): the
  * two differ in the first launch only, K_pair or K_pair_region.  After wtz_set_window_chaining(ctx, 0) that launch is K_pair_chain for both: the whole form is
@@ -67,131 +76,61 @@ static int pairs_seed_run(wtz_ctx_t *c, const char *who, const uint32_t *qid, co
 	wtz_timer t1; t1.start();
 	const char *kname = chain ? "K_pair_chain" : beg ? "K_pair_region" : "K_pair";
 	STAGE(c, kname);
-#if defined(WTZ_DEBUG_CRUMBS) && !defined(WTZ_EMUL)
-	unsigned int *h_crumbs = NULL;
-	if(getenv("WTZ_DEBUG_CRUMBS")){
-		HIPCHK(hipHostMalloc((void**)&h_crumbs, (size_t)n * 4, hipHostMallocCoherent | hipHostMallocMapped)); memset(h_crumbs, 0, (size_t)n * 4);
-		unsigned int *dptr = NULL; HIPCHK(hipHostGetDevicePointer((void**)&dptr, h_crumbs, 0));
-		HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(wtz_crumbs), &dptr, sizeof dptr));
-		g_crumbs = h_crumbs; g_crumbs_n = n; g_crumbs_q = qid; g_crumbs_c = cid;
-		signal(SIGABRT, wtz_crumbs_dump); signal(SIGPIPE, wtz_crumbs_dump); signal(SIGSEGV, wtz_crumbs_dump); signal(SIGBUS, wtz_crumbs_dump); signal(SIGTERM, wtz_crumbs_dump);
-	}
-#endif
-	/* XCD-aware task order: workgroups are dealt round-robin over the 8 XCDs, each with its own L2, and the pairs of a range are listed query by
-	 * query (about 30 candidates each), all of them searching the same query-side z-mer tables.  With the identity mapping an XCD's ~640 resident
-	 * waves hold every 8th pair of a 5 000-pair stretch, i.e. the tables of ~170 queries (20 MB against 4 MB of L2); giving every XCD runs of
-	 * `xg` CONSECUTIVE pairs makes that ~25 queries.  (WTZ_XCD_GROUP=0: identity.) */
-	const uint32_t xg = c->sw.xcd_group;
-	/* Heavy pairs first (round 4).  A pair's work grows faster than linearly with its matches (~ len(q) * len(c) / 78 732 chance matches of 10-mers alone), and
-	 * once the average dmo pair took a few ms the launch of a range ended with ONE wave still on a pair of 6 000 - 24 000 matches (100 - 230 M cycles of a
-	 * 120 - 170 ms launch: phase profile).  The n / 32 pairs with the largest len(q) * len(c) therefore head the task order (largest first); the others keep
-	 * the plan order - consecutive pairs share their query's tables - under the XCD mapping below.  WTZ_PAIR_HEAVY_FIRST=0 / 1 overrides the engine default
-	 * (dmo on; zmo off: its launches were measured full to the end). */
 	uint32_t nh = 0; const uint32_t *d_ord = NULL;
-#ifndef WTZ_EMUL
-	if(c->sw.heavy_first >= 0 ? c->sw.heavy_first != 0 : c->P.dot_matrix != 0){
-		nh = n / 32u;
-		if(nh >= 8u){
-			std::vector<uint64_t> key(n); std::vector<uint32_t> ord(n), hv(n);
-			for(uint32_t i = 0; i < n; i++){ key[i] = (uint64_t)c->h_rdlen[qid[i]] * c->h_rdlen[cid[i]]; hv[i] = i; }
-			std::nth_element(hv.begin(), hv.begin() + nh, hv.end(), [&](uint32_t a, uint32_t b){ return key[a] != key[b] ? key[a] > key[b] : a < b; });
-			std::sort(hv.begin(), hv.begin() + nh, [&](uint32_t a, uint32_t b){ return key[a] != key[b] ? key[a] > key[b] : a < b; });
-			std::vector<uint8_t> heavy(n, 0);
-			for(uint32_t k = 0; k < nh; k++){ ord[k] = hv[k]; heavy[hv[k]] = 1; }
-			uint32_t w = nh; for(uint32_t i = 0; i < n; i++) if(!heavy[i]) ord[w++] = i;
-			uint32_t *dd = NULL; CHK(dev_alloc((void**)&dd, (size_t)n * 4)); CHK(dev_h2d(dd, ord.data(), (size_t)n * 4)); d_ord = dd;
-		} else nh = 0;
-	}
-#endif
-	const uint64_t n64 = n - nh; const uint64_t nh64 = nh;
+	CHK(pairs_heavy_first(c, qid, cid, n, &d_ord, &nh));
+	const wtz_pair_order order = { nh, n - nh, c->sw.xcd_group, d_ord };
+	/* ---- the first launch: every pair ---- */
 #ifdef WTZ_EMUL
-	if(chain) CHK(wtz_launch_coop<K_pair_chain>(n, [=] WTZ_LAMBDA (uint64_t b){ wtz_task_pair<-1, true, true, true>((uint32_t)b, V, dq, dc, dr, d_beg, d_end); }, WTZ_PAIR_LDS_BYTES));
-	else if(beg) CHK(wtz_launch_coop<K_pair_region>(n, [=] WTZ_LAMBDA (uint64_t b){ wtz_task_pair<-1, true, true>((uint32_t)b, V, dq, dc, dr, d_beg, d_end); }, WTZ_PAIR_LDS_BYTES));
-	else
-	CHK(wtz_launch_coop<K_pair>(n, [=] WTZ_LAMBDA (uint64_t b){ (void)xg; (void)n64; (void)nh64; (void)d_ord; wtz_task_pair<-1>((uint32_t)b, V, dq, dc, dr); }, c->P.dot_matrix ? WTZ_PAIR_DM_LDS_BYTES : WTZ_PAIR_LDS_BYTES));
+	/* the host emulation: one loop over the pairs in the caller's order, engine and form chosen per call (ENGINE = -1) */
+	(void)order;
+	CHK(wtz_launch_coop<K_pair>(n, [=] WTZ_LAMBDA (uint64_t b){
+		if(chain) wtz_task_pair<-1, true, true>((uint32_t)b, V, dq, dc, dr, d_beg, d_end);
+		else if(d_beg) wtz_task_pair<-1, true>((uint32_t)b, V, dq, dc, dr, d_beg, d_end);
+		else wtz_task_pair<-1>((uint32_t)b, V, dq, dc, dr); }, c->P.dot_matrix ? WTZ_PAIR_DM_LDS_BYTES : WTZ_PAIR_LDS_BYTES));
 #else
-	if(chain){
-		CHK(wtz_launch_coop<K_pair_chain>(n, [=] WTZ_LAMBDA (uint64_t b){ wtz_task_pair<0, true, true, true>((uint32_t)b, V, dq, dc, dr, d_beg, d_end); }, WTZ_PAIR_LDS_BYTES));
-	} else if(beg){
-		/* the pairs in the caller's order: the pairs of a layout share ONE query table, the backbone's, so there is nothing for the XCD mapping of K_pair to keep together */
-		CHK(wtz_launch_coop<K_pair_region>(n, [=] WTZ_LAMBDA (uint64_t b){ wtz_task_pair<0, true, true>((uint32_t)b, V, dq, dc, dr, d_beg, d_end); }, WTZ_PAIR_LDS_BYTES));
-	} else if(c->P.dot_matrix){
-		CHK(wtz_launch_coop<K_pair_dm>(n, [=] WTZ_LAMBDA (uint64_t b){
-			uint64_t t = b;
-			if(b >= nh64){ const uint64_t b2 = b - nh64; t = b2; if(xg){ const uint64_t per = 8ull * xg, full = n64 / per * per; if(b2 < full){ const uint64_t r = b2 % per; t = b2 - r + (r & 7u) * xg + (r >> 3); } } t += nh64; }
-			if(d_ord) t = d_ord[t];
-			wtz_task_pair<1>((uint32_t)t, V, dq, dc, dr); }, WTZ_PAIR_DM_LDS_BYTES));
-	} else {
-		CHK(wtz_launch_coop<K_pair>(n, [=] WTZ_LAMBDA (uint64_t b){
-			uint64_t t = b;
-			if(b >= nh64){ const uint64_t b2 = b - nh64; t = b2; if(xg){ const uint64_t per = 8ull * xg, full = n64 / per * per; if(b2 < full){ const uint64_t r = b2 % per; t = b2 - r + (r & 7u) * xg + (r >> 3); } } t += nh64; }
-			if(d_ord) t = d_ord[t];
-#ifdef WTZ_PAIR_TWO_LAUNCH
-			wtz_task_pair<0, false>((uint32_t)t, V, dq, dc, dr); }, WTZ_PAIR_LDS_BYTES));       /* experiment: pairs with ranges beyond the LDS slice are marked and finished by K_pair_zbig */
-#else
-			wtz_task_pair<0, true>((uint32_t)t, V, dq, dc, dr); }, WTZ_PAIR_LDS_BYTES));
-#endif
-	}
-#endif
-#if defined(WTZ_DEBUG_CRUMBS) && !defined(WTZ_EMUL)
-	if(h_crumbs){
-		const double t0 = wtz_wall(); const double limit = atof(getenv("WTZ_DEBUG_CRUMBS")) > 1 ? atof(getenv("WTZ_DEBUG_CRUMBS")) : 20.0;
-		while(hipStreamQuery(g_stream) == hipErrorNotReady && wtz_wall() - t0 < limit){ struct timespec ts = {0, 50000000}; nanosleep(&ts, NULL); }
-		if(hipStreamQuery(g_stream) == hipErrorNotReady){
-			unsigned hist[256]; memset(hist, 0, sizeof hist); unsigned shown = 0;
-			for(uint32_t i = 0; i < n; i++) hist[h_crumbs[i] & 0xFF]++;
-			fprintf(stderr, "[crumbs] K_pair still running after %.0f s, %u pairs; tasks per last point:", limit, n);
-			for(int k = 0; k < 256; k++) if(hist[k]) fprintf(stderr, " %d:%u", k, hist[k]);
-			fprintf(stderr, "\n");
-			for(uint32_t i = 0; i < n && shown < 12; i++) if((h_crumbs[i] & 0xFF) != 0xFF && (h_crumbs[i] & 0xFF) != 0){ fprintf(stderr, "[crumbs]   pair %u (q %u, c %u): point %u, hits %u\n", i, qid[i], cid[i], h_crumbs[i] & 0xFF, h_crumbs[i] >> 8); shown++; }
-			fflush(stderr); _exit(86);
-		}
-	}
+	/* K_pair_chain and K_pair_region take the pairs in the caller's order: the pairs of a layout share ONE query table, the backbone's, so there is nothing for the XCD mapping to keep together */
+	if(chain)                 CHK(wtz_launch_coop<K_pair_chain>(n, [=] WTZ_LAMBDA (uint64_t b){ wtz_task_pair<0, true, true>((uint32_t)b, V, dq, dc, dr, d_beg, d_end); }, WTZ_PAIR_LDS_BYTES));
+	else if(beg)              CHK(wtz_launch_coop<K_pair_region>(n, [=] WTZ_LAMBDA (uint64_t b){ wtz_task_pair<0, true>((uint32_t)b, V, dq, dc, dr, d_beg, d_end); }, WTZ_PAIR_LDS_BYTES));
+	else if(c->P.dot_matrix)  CHK(wtz_launch_coop<K_pair_dm>(n, [=] WTZ_LAMBDA (uint64_t b){ wtz_task_pair<1>(order(b), V, dq, dc, dr); }, WTZ_PAIR_DM_LDS_BYTES));
+	else                      CHK(wtz_launch_coop<K_pair>(n, [=] WTZ_LAMBDA (uint64_t b){ wtz_task_pair<0>(order(b), V, dq, dc, dr); }, WTZ_PAIR_LDS_BYTES));
 #endif
 	CHK(dev_sync());
 	{ const double ms1 = t1.stop(); if(c->sw.profile) fprintf(stderr, "[pair-profile] %s first launch: %u pairs, %.1f ms\n", kname, n, ms1); }
 	c->n_pairs = n; c->h_pairres.resize(n); c->have_pairs = true;
 	CHK(dev_d2h(c->h_pairres.data(), c->d_pairres, (size_t)n * sizeof(wtz_pairres_t)));
-#ifndef WTZ_EMUL
-	if(!c->P.dot_matrix){
-		/* zmo pairs with a window range that does not fit the LDS slice (hundreds of matches of one strand inside one window: repeats) were left by the first launch:
-		 * the launch that carries the pool-workspace body of the scan finishes them (round 3 ran those scans on lane 0 and the heaviest pair bounded its launch) */
+	/* ---- the finishers: a launch over the pairs of h_pairres that `want` picks (a device list of their indexes), the results read back; *n_list = how many ---- */
+	auto finish = [&](const char *stage, const char *what, auto want, auto launch, size_t *n_list) -> int {
 		std::vector<uint32_t> list;
-		for(uint32_t i = 0; i < n; i++) if(c->h_pairres[i].gate && c->h_pairres[i].dm_dir == WTZ_PAIR_NEEDS_ZBIG && !c->h_pairres[i].bad) list.push_back(i);
-		if(!list.empty()){
-			uint32_t *d_list = NULL; CHK(dev_alloc((void**)&d_list, list.size() * 4)); CHK(dev_h2d(d_list, list.data(), list.size() * 4));
-			wtz_timer tt; tt.start();
-			STAGE(c, "K_pair_zbig");
-			CHK(wtz_launch_coop<K_pair_zbig>(list.size(), [=] WTZ_LAMBDA (uint64_t t){ wtz_task_pair<0, true>(d_list[t], V, dq, dc, dr); }, WTZ_PAIR_LDS_BYTES));
-			CHK(dev_sync());
-			const double ms_t = tt.stop();
-			CHK(dev_d2h(c->h_pairres.data(), c->d_pairres, (size_t)n * sizeof(wtz_pairres_t)));
-			if(c->sw.profile) fprintf(stderr, "[pair-profile] zmo pairs with ranges beyond the LDS slice: %zu of %u, %.1f ms\n", list.size(), n, ms_t);
-		}
-	}
-#endif
+		for(uint32_t i = 0; i < n; i++) if(want(c->h_pairres[i])) list.push_back(i);
+		*n_list = list.size();
+		if(list.empty()) return WTZ_OK;
+		uint32_t *d_list = NULL; CHK(dev_alloc((void**)&d_list, list.size() * 4)); CHK(dev_h2d(d_list, list.data(), list.size() * 4));
+		wtz_timer tt; tt.start();
+		STAGE(c, stage);
+		CHK(launch(d_list, list.size()));
+		CHK(dev_sync());
+		const double ms_t = tt.stop();
+		CHK(dev_d2h(c->h_pairres.data(), c->d_pairres, (size_t)n * sizeof(wtz_pairres_t)));
+		if(c->sw.profile) fprintf(stderr, "[pair-profile] %s: %zu pairs, %.1f ms\n", what, list.size(), ms_t);
+		return WTZ_OK;
+	};
 	if(c->P.dot_matrix){
-		/* pairs whose strand images exceed the LDS slice of K_pair are finished by launches with larger slices: few pairs,
+		/* pairs whose strand images exceed the LDS slice of K_pair_dm are finished by launches with larger slices: few pairs,
 		 * but they are the long ones that would otherwise bound the batch from a single lane */
 		uint32_t tiers[3] = { WTZ_PAIR_DM_LDS_TIER2, WTZ_PAIR_DM_LDS_TIER3, WTZ_PAIR_DM_LDS_TIER4 };
 		if(getenv("WTZ_DM_TIER3_KB")) tiers[1] = (uint32_t)atoi(getenv("WTZ_DM_TIER3_KB")) << 10;
 		if(getenv("WTZ_DM_TIER4_KB")) tiers[2] = (uint32_t)atoi(getenv("WTZ_DM_TIER4_KB")) << 10;
 		/* with the pool image allowed in the first launch only what overflowed its group table or band list is left: the last launch's */
 		for(int tier = c->sw.dm_first_big ? 2 : 0; tier < 3; tier++){
-			std::vector<uint32_t> list;
-			for(uint32_t i = 0; i < n; i++) if(c->h_pairres[i].gate && c->h_pairres[i].dm_dir == -2 && !c->h_pairres[i].bad) list.push_back(i);
-			if(list.empty()) break;
-			uint32_t *d_list = NULL; CHK(dev_alloc((void**)&d_list, list.size() * 4)); CHK(dev_h2d(d_list, list.data(), list.size() * 4));
 			const uint32_t lb = tiers[tier]; const bool last = (tier == 2), big = (tier >= 1);
-			wtz_timer tt; tt.start();
-			STAGE(c, "K_pair_big");
-			CHK(wtz_launch_coop<K_pair_big>(list.size(), [=] WTZ_LAMBDA (uint64_t t){ wtz_task_pair_dm_big((uint32_t)t, V, d_list, dq, dc, dr, lb, last, big); }, lb));
-			CHK(dev_sync());
-			const double ms_t = tt.stop();
-			CHK(dev_d2h(c->h_pairres.data(), c->d_pairres, (size_t)n * sizeof(wtz_pairres_t)));
-			if(c->sw.profile) fprintf(stderr, "[pair-profile] dmo tier %d (%u KB LDS): %zu pairs, %.1f ms\n", tier + 2, lb >> 10, list.size(), ms_t);
+			char what[64]; snprintf(what, sizeof what, "dmo tier %d (%u KB LDS)", tier + 2, lb >> 10);
+			size_t left = 0;
+			CHK(finish("K_pair_big", what, [](const wtz_pairres_t &r){ return r.gate && r.dm_dir == -2 && !r.bad; }, [=](const uint32_t *d_list, size_t k){
+				return wtz_launch_coop<K_pair_big>(k, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_pair_dm_big((uint32_t)t, V, d_list, dq, dc, dr, lb, last, big); }, lb); }, &left));
+			if(left == 0) break;
 		}
 	}
+	/* ---- counters, profile, summaries ---- */
 	c->cnt.ms_pairs += tm.stop(); c->cnt.n_pairs += n;
 	for(uint32_t i = 0; i < n; i++) c->cnt.bytes_zmer_algo += (uint64_t)c->h_rdlen[cid[i]] / 4 + 16ull * c->h_pairres[i].n_hits;
 	CHK(pool_check(c, who));

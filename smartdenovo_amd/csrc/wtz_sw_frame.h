@@ -300,16 +300,11 @@ WTZ_D wtz_aln_t wtz_extend_shift_fr(int32_t qlen, const wtz_seq_packed &query, i
 				}
 			}
 		}
-#ifndef WTZ_EXP_NOTRACE
 		if(colrel0 < nvt){
 			WTZ_GLOBAL_AS uint32_t *zr = wtz_as_global((uint32_t*)(z + (size_t)(i & 63) * zrow) + lane);
 			#pragma unroll
 			for(int q4 = 0; q4 < C4; q4++) zr[(size_t)q4 * 64] = zw[q4];
 		}
-#endif
-#ifdef WTZ_EXP_ROWS1
-		stop = true;       /* diagnostic build: one row per job (the fixed cost of a job; results are wrong) */
-#endif
 		if(stop) break;
 	}
 	if(cells && lane == 0) *cells += ncell;

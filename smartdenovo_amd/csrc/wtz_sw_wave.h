@@ -522,9 +522,6 @@ WTZ_D bool wtz_shift_traceback(wtz_aln_t &x, uint8_t **zchunk, const int32_t *zb
 	static_assert(NDW <= 64 && ROWB <= 128, "window geometry");
 	uint32_t *S32 = (uint32_t*)tb; uint8_t *S8 = (uint8_t*)tb; uint8_t *Sd = S8 + 8192;
 	int32_t i_ = x.qe, j_ = x.te; uint32_t d_ = 0;
-#ifdef WTZ_EXP_NOTB
-	i_ = -1; j_ = -1;      /* diagnostic build: no traceback (results are wrong) */
-#endif
 	uint32_t run_op = 0xFFu, run_len = 0;
 	int32_t n_gap_runs = 0; bool consistent = true;
 	wtz_cigw_t Wr; Wr.v = &cigars; Wr.tail = 0;

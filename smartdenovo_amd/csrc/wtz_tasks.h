@@ -43,28 +43,36 @@ WTZ_D int32_t *wtz_wave_scratch(){ extern __shared__ int32_t wtz_dyn_lds[]; retu
 WTZ_COOP_HOST int32_t *wtz_wave_scratch(){ return NULL; }
 #endif
 
-/* -DWTZ_DEBUG_CRUMBS: every pair task leaves its last reached point in a host-visible array, so that a hung or faulting K_pair launch
- * can be located from the host (WTZ_DEBUG_CRUMBS=1 makes wtz_pairs_seed poll instead of waiting and report the stragglers) */
-#if defined(WTZ_DEBUG_CRUMBS) && defined(__HIPCC__)
-__device__ unsigned int *wtz_crumbs = NULL;
-#endif
-#if defined(WTZ_DEBUG_CRUMBS) && defined(__HIP_DEVICE_COMPILE__)
-#define WTZ_CRUMB(t, code) do { if(wtz_crumbs && WTZ_LANE == 0) __hip_atomic_store(&wtz_crumbs[t], (unsigned int)(code), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); } while(0)
-#else
-#define WTZ_CRUMB(t, code) do { } while(0)
-#endif
+/* The task order of the K_pair / K_pair_dm launches: block index -> pair index, a bijection on [0, nh + n_rest).
+ * Heavy pairs first (round 4).  A pair's work grows faster than linearly with its matches (~ len(q) * len(c) / 78 732 chance matches of 10-mers alone), and
+ * once the average dmo pair took a few ms the launch of a range ended with ONE wave still on a pair of 6 000 - 24 000 matches (100 - 230 M cycles of a
+ * 120 - 170 ms launch: phase profile).  The `nh` pairs with the largest len(q) * len(c) therefore head the task order (largest first, through `ord`); the
+ * n_rest others keep the plan order - consecutive pairs share their query's tables - under the XCD mapping.  `ord` == NULL: no list, nh = 0.
+ * XCD-aware order behind them: workgroups are dealt round-robin over the 8 XCDs, each with its own L2, and the pairs of a range are listed query by
+ * query (about 30 candidates each), all of them searching the same query-side z-mer tables.  With the identity mapping an XCD's ~640 resident
+ * waves hold every 8th pair of a 5 000-pair stretch, i.e. the tables of ~170 queries (20 MB against 4 MB of L2); giving every XCD runs of
+ * `xg` CONSECUTIVE pairs makes that ~25 queries.  The last, incomplete group of 8 * xg keeps the identity.  (xg = 0, WTZ_XCD_GROUP=0: identity.) */
+struct wtz_pair_order {
+	uint64_t nh, n_rest; uint32_t xg; const uint32_t *ord;
+	WTZ_HDM uint32_t operator()(uint64_t b) const {
+		uint64_t t = b;
+		if(b >= nh){ const uint64_t b2 = b - nh; t = b2; if(xg){ const uint64_t per = 8ull * xg, full = n_rest / per * per; if(b2 < full){ const uint64_t r = b2 % per; t = b2 - r + (r & 7u) * xg + (r >> 3); } } t += nh; }
+		if(ord) t = ord[t];
+		return (uint32_t)t;
+	}
+};
+
 /* all lanes of the wavefront enter; the z-mer matching is cooperative, the order-sensitive remainder runs on lane 0 */
 /* ENGINE: 0 = windows + chain (zmo), 1 = dot matrix (dmo), -1 = decided at run time (host emulation).  One kernel per engine (round 3): a zmo launch does not
  * carry the registers and code of the dot-matrix path and vice versa. */
-/* ZBIG (zmo): the window scans may use a workspace in the pool when a range does not fit the LDS slice.  The first launch runs without that body (its registers
- * and code would be carried by every pair) and marks the few pairs that need it (dm_dir = WTZ_PAIR_NEEDS_ZBIG); a second launch finishes them. */
-#define WTZ_PAIR_NEEDS_ZBIG (-3)
+/* zmo: a window scan whose matches do not fit the LDS slice runs on a workspace in the pool, in the same launch: the body is a function of its own
+ * (wtz_scan_windows_rest_pool, wtz_window.h), reached by a handful of pairs. */
 /* REGION: align_hzmaux with beg / end (wtmsa's call, wtmsa.c:448-477): the z-mer matches of pair t are those of the interval [reg_beg[t], reg_end[t]) of the
  * query, the indexed side (wtz_zmatch_coop<true>); the host has applied the defaults of hzm_aln.h:1690-1691.  Everything behind the matches is blind to the
  * interval, as in the reference (hzm_aln.h:1696-1718).  A launch of its own (wtz_pairs_seed_region): the form without an interval does not carry the test. */
 /* CHAIN: the windows of a scan by chaining_hzmps (HZM_FAST_WINDOW_KMER_CHAINING = 0, as wtmsa and wtcns set it: wtz_set_window_chaining, wtz_window.h), a launch of
  * its own (K_pair_chain): the other forms do not carry the branch. */
-template<int ENGINE = -1, bool ZBIG = true, bool REGION = false, bool CHAIN = false>
+template<int ENGINE = -1, bool REGION = false, bool CHAIN = false>
 WTZ_HD void wtz_task_pair(uint32_t t, const wtz_env_t &V, const uint32_t *qid, const uint32_t *cid, wtz_pairres_t *res, const int32_t *reg_beg = NULL, const int32_t *reg_end = NULL){
 	const wtz_params_t *P = V.P;
 	const int32_t rtb = REGION ? reg_beg[t] : 0, rte = REGION ? reg_end[t] : 0;
@@ -78,7 +86,6 @@ WTZ_HD void wtz_task_pair(uint32_t t, const wtz_env_t &V, const uint32_t *qid, c
 #define WTZ_TICK() ((uint64_t)0)
 #endif
 	const uint64_t tk0 = WTZ_TICK();
-	WTZ_CRUMB(t, 1);
 	const bool aux = P->aux_strand != 0;                     /* align_hzmaux's form of the pair stages (wtgbo): strand 0 only, no n_hits gate */
 #if defined(__HIP_DEVICE_COMPILE__)
 	const bool ok0 = wtz_zmatch_coop<REGION>(V.ZQ, V.Z, q, c, V.R.rdlen[c], P->max_kmer_var, V.pool, &hits, &n, aux, (uint32_t*)wtz_wave_scratch(), dm ? (uint32_t)WTZ_PAIR_DM_LDS_BYTES : (uint32_t)WTZ_PAIR_LDS_BYTES, rtb, rte);      /* the LDS slice is free until the first ordering */
@@ -90,7 +97,6 @@ WTZ_HD void wtz_task_pair(uint32_t t, const wtz_env_t &V, const uint32_t *qid, c
 	n = wtz_coop_bcast32(n);
 	hits = (wtz_zhit_t*)(uintptr_t)wtz_coop_bcast64((uint64_t)(uintptr_t)hits);
 	const uint64_t tk1 = WTZ_TICK();
-	WTZ_CRUMB(t, 2 | (n << 8));
 	wtz_zhit_t *sorted = NULL;
 #if defined(__HIP_DEVICE_COMPILE__)
 	__threadfence_block();
@@ -103,10 +109,9 @@ WTZ_HD void wtz_task_pair(uint32_t t, const wtz_env_t &V, const uint32_t *qid, c
 	}
 #endif
 	const uint32_t lane = WTZ_LANE;
-	WTZ_CRUMB(t, 3 | (n << 8));
-	if(!ok || r.bad){ r.bad = 1; if(lane == 0) res[t] = r; WTZ_CRUMB(t, 0xFF); return; }
+	if(!ok || r.bad){ r.bad = 1; if(lane == 0) res[t] = r; return; }
 	r.n_hits = n;
-	if(aux ? n == 0 : n * P->zsize < P->ztot){ r.gate = 0; if(lane == 0) res[t] = r; WTZ_CRUMB(t, 0xFF); return; }
+	if(aux ? n == 0 : n * P->zsize < P->ztot){ r.gate = 0; if(lane == 0) res[t] = r; return; }
 	r.gate = 1;
 	if(dm){
 		wtz_vec<wtz_zhit_t> cache; cache.a = sorted ? sorted : hits; cache.n = n; cache.cap = n + 2; cache.pool = V.pool; cache.bad = 0;
@@ -127,8 +132,7 @@ WTZ_HD void wtz_task_pair(uint32_t t, const wtz_env_t &V, const uint32_t *qid, c
 	}
 	/* zmo: every lane follows the window merge (uniform control flow); the vectors belong to lane 0 */
 	if(sorted) hits = sorted;                                                             /* tie-free: the unique ascending order */
-	else { WTZ_CRUMB(t, 4 | (n << 8)); if(lane == 0) wtz_sort_exact(hits, (size_t)n, wtz_gt_off12()); WTZ_WAVE_SYNC(); }   /* process_hzmps, hzm_aln.h:1184-1186, swap-exact */
-	WTZ_CRUMB(t, 5 | (n << 8));
+	else { if(lane == 0) wtz_sort_exact(hits, (size_t)n, wtz_gt_off12()); WTZ_WAVE_SYNC(); }   /* process_hzmps, hzm_aln.h:1184-1186, swap-exact */
 	const uint64_t tk2 = WTZ_TICK();
 	wtz_winscratch_t sc;
 	{
@@ -137,7 +141,7 @@ WTZ_HD void wtz_task_pair(uint32_t t, const wtz_env_t &V, const uint32_t *qid, c
 		pa = wtz_coop_bcast64(pa);
 		sc.ts = (uint32_t*)(uintptr_t)pa;
 	}
-	if(sc.ts == NULL){ r.bad = 1; if(lane == 0) res[t] = r; WTZ_CRUMB(t, 0xFF); return; }
+	if(sc.ts == NULL){ r.bad = 1; if(lane == 0) res[t] = r; return; }
 	sc.as = (int32_t*)(sc.ts + (n + 2)); sc.wb = sc.ts + 2 * (n + 2); sc.we = sc.ts + 3 * (n + 2); sc.wo = sc.ts + 4 * (n + 2); sc.wf = sc.ts + 5 * (n + 2); sc.wd = sc.ts + 6 * (n + 2);
 	sc.tk = (uint64_t*)(sc.ts + 7 * (n + 2) + ((7 * (n + 2)) & 1)); sc.ztmp = (wtz_zhit_t*)(sc.tk + (n + 2));
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -147,29 +151,16 @@ WTZ_HD void wtz_task_pair(uint32_t t, const wtz_env_t &V, const uint32_t *qid, c
 	sc.lds = emul_lds;
 #endif
 	sc.lds_u64 = WTZ_PAIR_LDS_BYTES / 8;
-	sc.big = NULL; sc.big_u64 = 0; sc.need_big = 0;
-#ifndef WTZ_MERGE_SCALAR
+	sc.big = NULL; sc.big_u64 = 0;
 	wtz_merge_prepare(hits, n, sc, P->kwin);
-#endif
 	for(uint32_t dir = 0; dir < 2; dir++){
 		wtz_vec<wtz_win_t> wins; wtz_vec<wtz_zhit_t> anchors;
 		wins.a = NULL; wins.n = wins.cap = 0; wins.pool = V.pool; wins.bad = 0;
 		anchors.a = NULL; anchors.n = anchors.cap = 0; anchors.pool = V.pool; anchors.bad = 0;
 		if(lane == 0){ wins.init(V.pool, 16); anchors.init(V.pool, n + 16); }
-		WTZ_CRUMB(t, (6 + dir) | (n << 8));
 		const unsigned long long ptm = WTZ_PROF_T(); (void)ptm;
-#ifdef WTZ_MERGE_SCALAR
-		const uint32_t nw = wtz_merge_windows_coop<ZBIG, CHAIN>(hits, n, dir, wins, anchors, sc, P->zsize, P->kwin, P->kstep, P->zovl);
-#else
-		const uint32_t nw = wtz_merge_windows_wave<ZBIG, CHAIN>(hits, n, dir, wins, anchors, sc, P->zsize, P->kwin, P->kstep, P->zovl);
-#endif
+		const uint32_t nw = wtz_merge_windows_wave<CHAIN>(hits, n, dir, wins, anchors, sc, P->zsize, P->kwin, P->kstep, P->zovl);
 		WTZ_PROF_ADD(63, ptm);      /* profiler: 63 = merge loop incl. its scans, 62 = chain + compaction */
-		if(!ZBIG && sc.need_big){          /* a range that does not fit the LDS slice: the whole pair again in the launch with the pool-workspace body */
-			if(lane == 0){ wtz_pairres_t r2; memset(&r2, 0, sizeof r2); r2.n_hits = r.n_hits; r2.gate = 1; r2.dm_dir = WTZ_PAIR_NEEDS_ZBIG; res[t] = r2; }
-			WTZ_CRUMB(t, 0xFF);
-			return;
-		}
-		WTZ_CRUMB(t, (8 + dir) | (n << 8));
 		/* the vectors belong to lane 0: what the chain needs of them as uniform values */
 		if(wtz_coop_bcast32((uint32_t)(wins.bad | anchors.bad))){ r.bad = 1; continue; }
 		if(nw == 0) continue;
@@ -194,7 +185,6 @@ WTZ_HD void wtz_task_pair(uint32_t t, const wtz_env_t &V, const uint32_t *qid, c
 	if(lane != 0) return;
 	{ const uint64_t tk3 = WTZ_TICK(); r.tick[0] = (uint32_t)((tk1 - tk0) >> 10); r.tick[1] = (uint32_t)((tk2 - tk1) >> 10); r.tick[2] = (uint32_t)((tk3 - tk2) >> 10); r.tick[3] = (uint32_t)((tk3 - tk0) >> 10); }
 	res[t] = r;
-	WTZ_CRUMB(t, 0xFF);
 }
 
 /* dmo pairs whose strand images did not fit the LDS slice of K_pair: same alignment over the already ordered matches, launched
@@ -1065,9 +1055,6 @@ WTZ_HD void wtz_task_stitch_mid(uint32_t t, const wtz_env_t &V, const wtz_alnite
 #else
 	std::vector<uint64_t> jbuf(3 * (size_t)(2u + 2u * nwr) + 1); uint32_t *jlds = (uint32_t*)jbuf.data(); const uint32_t jwords = (uint32_t)(jbuf.size() * 2);
 #endif
-#ifdef WTZ_NO_CIGAR_JOIN
-	const bool joined = false; (void)jlds; (void)jwords; (void)lc;
-#else
 	const bool joined = wtz_cigar_join_coop(st.cigar, 2u + 2u * nwr, [=](uint32_t p, const uint32_t **src, uint32_t *n, uint32_t *rev){
 		*rev = 0;
 		if(p == 0){ *src = lc; *n = ln; *rev = 1; return; }
@@ -1076,7 +1063,6 @@ WTZ_HD void wtz_task_stitch_mid(uint32_t t, const wtz_env_t &V, const wtz_alnite
 		if(regs[k].pass != 1){ *src = NULL; *n = 0; return; }
 		if(p & 1u){ *src = regs[k].cigar; *n = regs[k].cigar_len; } else { *src = gp[k].cigar; *n = gp[k].cigar_len; }
 	}, jlds, jwords);
-#endif
 	if(!joined){
 		if(ln){ wtz_cigar_reverse_coop(jobsL[t].cigar, ln); wtz_cigar_concat_coop(st.cigar, jobsL[t].cigar, ln); }
 		wtz_cigar_concat_coop(st.cigar, regs[first].cigar, regs[first].cigar_len);

@@ -2,7 +2,7 @@
  * wtz_window.h — per-pair task bodies: z-mer matching (A6), the (off1,off2) ordering, window
  * detection and window chaining of the zmo engine (A7z).
  *
- *   wtz_zmatch            hzm_aln.h:173-224   query_single_read_seeds against the prebuilt tables
+ *   wtz_zmatch_coop       hzm_aln.h:173-224   query_single_read_seeds against the prebuilt tables (REGION: hzm_aln.h:117-171)
  *   wtz_scan_windows_coop hzm_aln.h:410-578   potential_paired_kmers_windows (fast chaining branch; its median, hzm_aln.h:316-343, is a rank selection on the sorting network)
  *   wtz_merge_windows_wave hzm_aln.h:580-656  merge_paired_kmers_window
  *   wtz_chain_windows_wave hzm_aln.h:658-713  chaining_wtseedv
@@ -20,35 +20,7 @@
 
 #define WTZ_KWIN_MAX_OFFSET_DEV 50
 
-/* ---- A6: walk the candidate's position-ordered z-mers, look each up in the query's table ---- */
-WTZ_HD bool wtz_zmatch(const wtz_zindex_t &ZQ, const wtz_zindex_t &ZC, uint32_t q, uint32_t c, uint32_t clen, uint32_t max_var, wtz_vec<wtz_zhit_t> &out, bool same_strand = false){
-	const uint64_t qo = ZQ.zoff[q], co = ZC.zoff[c];      /* ZQ: the index holding the query's table (A5), ZC: the one holding the candidate's position-ordered z-mers (the same index unless the caller split them) */
-	const uint32_t cn = (uint32_t)(ZC.zoff[c + 1] - co), qd = ZQ.dn[q];
-	const uint32_t *dmer = ZQ.dmer + qo;
-	for(uint32_t k = 0; k < cn; k++){
-		if(!ZC.ok[co + k]) continue;                       /* per-table-entry hit cap (hzm_aln.h:208-211) */
-		uint32_t m = ZC.mer[co + k];
-		uint32_t lo = 0, hi = qd;
-		while(lo < hi){ uint32_t mid = (lo + hi) >> 1; if(dmer[mid] < m) lo = mid + 1; else hi = mid; }
-		if(lo >= qd || dmer[lo] != m) continue;
-		uint32_t cpos = ZC.pos[co + k], clen2 = ZC.len[co + k];
-		uint32_t first = ZQ.dfirst[qo + lo], cnt = ZQ.dcnt[qo + lo];
-		for(uint32_t e = 0; e < cnt; e++){
-			uint32_t qi = ZQ.sidx[qo + first + e];
-			uint32_t qpos = ZQ.pos[qo + qi], qlen = ZQ.len[qo + qi];
-			uint32_t dv = qlen > clen2 ? qlen - clen2 : clen2 - qlen;
-			if(dv > max_var) continue;
-			uint32_t d1 = qpos & 1u, d2 = cpos & 1u;
-			if(same_strand && (d1 ^ d2)) continue;           /* align_hzmaux: filter_by_region_hzmps(dir 0), hzm_aln.h:1193 */
-			uint32_t off2 = (d1 ^ d2) ? clen - ((cpos >> 1) + clen2) : (cpos >> 1);
-			wtz_zhit_t h; h.o1 = (d1 << 31) | (qpos >> 1); h.o2 = (d2 << 31) | off2; h.ll = (clen2 << 16) | qlen; h.gid = 0;
-			if(!out.push(h)) return false;
-		}
-	}
-	return true;
-}
-
-/* A6, wave-cooperative: lanes take consecutive candidate z-mers, the matches of a 64-z-mer chunk are written in
+/* A6 (walk the candidate's position-ordered z-mers, look each up in the query's table), wave-cooperative: lanes take consecutive candidate z-mers, the matches of a 64-z-mer chunk are written in
  * candidate-position order through an exclusive scan of the per-lane match counts (emission order is part of the
  * contract: hzm_aln.h:212-221).  Passes: (round 4) prefilter + ordered compaction, count (the dense index of each surviving z-mer is
  * cached), allocate exactly, fill.
@@ -211,8 +183,6 @@ WTZ_HD bool wtz_zmatch_coop(const wtz_zindex_t &ZQ, const wtz_zindex_t &ZC, uint
 
 struct wtz_gt_off12 { WTZ_HDM bool operator()(const wtz_zhit_t &a, const wtz_zhit_t &b) const {
 	uint64_t ka = ((uint64_t)ZH_OFF1(a) << 32) | ZH_OFF2(a), kb = ((uint64_t)ZH_OFF1(b) << 32) | ZH_OFF2(b); return ka > kb; } };
-struct wtz_gt_off1 { WTZ_HDM bool operator()(const wtz_zhit_t &a, const wtz_zhit_t &b) const { return ZH_OFF1(a) > ZH_OFF1(b); } };
-struct wtz_gt_idx_off2 { const wtz_zhit_t *rs; WTZ_HDM bool operator()(uint32_t a, uint32_t b) const { return ZH_OFF2(rs[a]) > ZH_OFF2(rs[b]); } };
 
 #if defined(__HIP_DEVICE_COMPILE__)
 /*
@@ -302,45 +272,59 @@ WTZ_D wtz_zhit_t *wtz_sort_hits_wave(const wtz_zhit_t *hits, uint32_t n, wtz_poo
 /* scratch of one (pair,strand) window scan: all sized by the number of matches of the pair.  `lds` (may be NULL) is the
  * wave's LDS slice: the small order-sensitive sorts / the quick-select run there when they fit - they are chains of
  * dependent loads on a single lane, so it is the access latency (LDS ~64 clk vs L2 ~500 clk) that matters */
-/* `big`: workspace in the pool for the scans whose matches do not fit the LDS slice (allocated by the first such scan of the pair, grown on demand);
- * `need_big`: set by a scan of the LDS-only kernel that met such a range - the pair is finished by the launch that carries the pool-workspace body */
+/* `big`, `big_u64`: workspace in the pool for the scans whose matches do not fit the LDS slice (allocated by the first such scan of the pair, grown on demand;
+ * the scan then runs in wtz_scan_windows_rest_pool, in the same launch) */
 /* `wf`, `wd` (n + 2 words each): the two per-match tables of the wave-parallel window merge (wtz_merge_prepare) */
-typedef struct { uint32_t *ts; int32_t *as; uint32_t *wb, *we, *wo; uint64_t *tk; wtz_zhit_t *ztmp; uint64_t *lds; uint32_t lds_u64; mutable uint64_t *big; mutable uint32_t big_u64; mutable uint32_t need_big; uint32_t *wf, *wd; } wtz_winscratch_t;
+typedef struct { uint32_t *ts; int32_t *as; uint32_t *wb, *we, *wo; uint64_t *tk; wtz_zhit_t *ztmp; uint64_t *lds; uint32_t lds_u64; mutable uint64_t *big; mutable uint32_t big_u64; uint32_t *wf, *wd; } wtz_winscratch_t;
 struct wtz_gt_hi32 { WTZ_HDM bool operator()(uint64_t a, uint64_t b) const { return (uint32_t)(a >> 32) > (uint32_t)(b >> 32); } };
 
 /*
- * Wave-cooperative form of the two functions above (same results).  What bounds a pair here is not arithmetic but the
- * latency of dependent loads on a single lane, so:
- *   - the merge loop reads the (off1,off2)-ordered matches through two 64-entry register windows (one hit per lane,
- *     fetched with one coalesced load; the uniform cursor reads them with v_readlane);
- *   - a window scan compacts its strand-filtered matches with ballot ranks, orders them by off2 with the wave-wide
- *     bitonic network (any off2 tie makes lane 0 redo the swap-exact sort from the original order - tie order is
- *     observable), and gathers them ONCE into LDS; the sequential sweep / median / anchor ordering of lane 0 then run
- *     out of LDS and registers only.
+ * The window scan and the merge loop around it are wave-cooperative.  What bounds a pair here is not arithmetic but the
+ * latency of dependent loads on a single lane, so a window scan compacts its strand-filtered matches with ballot ranks,
+ * orders them by off2 with the wave-wide bitonic network (an observable off2 tie makes lane 0 redo the swap-exact sort
+ * from the original order), and gathers them ONCE into LDS; the sweep, the median and the anchor ordering then run
+ * out of LDS and registers only.
  * Vectors (`wins`, `anchors`) are owned by lane 0; counts and the window extent the merge loop needs are broadcast.
- * A scan whose matches do not fit the LDS slice (np + 2n + 2 > lds_u64 words) falls back to the scalar body on lane 0.
+ * A scan whose matches do not fit the LDS slice (np + 2n + 2 > lds_u64 words) runs the same body on a workspace in the pool.
  */
-typedef struct { uint32_t base, o1, o2, ll; } wtz_hitcur_t;        /* lane l holds match base + l */
-WTZ_HD void wtz_hitcur_get(wtz_hitcur_t &c, const wtz_zhit_t *rs, uint32_t lim, uint32_t i, uint32_t &o1, uint32_t &o2, uint32_t &ll){
-	if(i - c.base >= WTZ_NLANES){           /* uniform; also true for i < base */
-		c.base = i;
-		const uint32_t idx = i + WTZ_LANE;
-		if(idx <= lim){ const wtz_zhit_t h = rs[idx]; c.o1 = h.o1; c.o2 = h.o2; c.ll = h.ll; } else { c.o1 = c.o2 = c.ll = 0; }
-	}
-	const uint32_t l = i - c.base;
-	o1 = wtz_coop_lane32(c.o1, l); o2 = wtz_coop_lane32(c.o2, l); ll = wtz_coop_lane32(c.ll, l);
+/* the strand / bound filter of a scan (the prefix skip of hzm_aln.h:425-431 is the same predicate: off1 is non-decreasing) */
+WTZ_HD bool wtz_scan_keeps(uint32_t o1, uint32_t o2, uint32_t dir, int32_t bound){ return (((o1 ^ o2) >> 31) == dir) && ((int32_t)(o1 & 0x7FFFFFFFu) >= bound); }
+/* ---- the exact early exit of a scan (round 3): can the sweep of hzm_aln.h:451-483 reach `ol >= zovl` at all?  In off2 order the running overlap is
+ * ol = sum of len2 over the in-window matches j..i minus the overlaps of neighbours (a match adds len2 minus its overlap with the one
+ * before, an eviction takes len2 minus the overlap with the one behind; ends are monotone in off2 for the matches of one strand), so
+ * ol <= sum of len2 over j..i, and the while loop keeps off2[i] - off2[j] < kwin: the in-window matches lie in nadj adjacent bins of
+ * kwin / 8 columns (nine bins = 1.125 kwin: eight would miss a window that starts late in its first bin).  If no such run of bins holds zovl bases of matches, no
+ * window can open, n2 stays 0 and the scan returns 0 - without the off2 ordering, the gather and the lane-0 sweep.  Tie order cannot matter: the bound is over sets.
+ * [mn, mx] = the off2 range of the kept matches (uniform); `each(f)` calls f(off2, len2) for every kept match of this lane; B = room for `cap` bins.
+ * Returns true when no window can open; false also when the bins do not fit B. ---- */
+template<typename EACH>
+WTZ_HD bool wtz_scan_cannot_open(uint32_t mn, uint32_t mx, EACH each, uint32_t *B, uint32_t cap, uint32_t kwin, uint32_t zovl){
+	const uint32_t lane = WTZ_LANE;
+	const uint32_t bw = kwin >= 8 ? kwin / 8 : 1;          /* bins of an eighth of the window: the in-window matches span < kwin columns = at most nadj adjacent bins */
+	const uint32_t nadj = (kwin - 1) / bw + 2;      /* the bins are aligned to mn, not to the window: kwin - 1 columns starting anywhere inside a bin reach into one more */
+	const uint32_t nb = (mx - mn) / bw + 1 + nadj;         /* nadj empty bins behind the last: every run of nadj bins starting at a used bin is inside the array */
+	if(nb > cap) return false;
+	for(uint32_t b = lane; b < nb; b += WTZ_NLANES) B[b] = 0;
+	WTZ_WAVE_SYNC();
+	each([&](uint32_t off2, uint32_t len2){
+		const uint32_t bin = (off2 - mn) / bw;
+#if defined(__HIP_DEVICE_COMPILE__)
+		atomicAdd(&B[bin], len2);
+#else
+		B[bin] += len2;
+#endif
+	});
+	WTZ_WAVE_SYNC();
+	uint32_t best = 0;
+	for(uint32_t b = lane; b + nadj <= nb; b += WTZ_NLANES){ uint32_t v = 0; for(uint32_t t = 0; t < nadj; t++) v += B[b + t]; best = v > best ? v : best; }
+	best = ~wtz_coop_min32(~best);
+	WTZ_WAVE_SYNC();                                  /* B is the caller's key array: written again behind this */
+	return best < zovl;
 }
 
-/* the part of a scan that only the scans past the early exits reach (one in seven at configs[2]): ordering, sweep, windows.  WTZ_SCAN_REST_FN / WTZ_SCAN_FN choose
- * whether it / the whole scan is inlined into the merge loop (WTZ_HD) or a function of its own (WTZ_HDN: the merge loop's cursors do not share the register file with this body) */
-#ifndef WTZ_SCAN_REST_FN
-#define WTZ_SCAN_REST_FN WTZ_HD
-#endif
-#ifndef WTZ_SCAN_FN
-#define WTZ_SCAN_FN WTZ_HD
-#endif
+/* the part of a scan that only the scans past the early exits reach (one in seven at configs[2]): ordering, sweep, windows */
 template<bool K_LDS, bool CHAIN = false>
-WTZ_SCAN_REST_FN uint32_t wtz_scan_windows_rest(const wtz_zhit_t *rs, uint32_t dir, uint32_t beg, uint32_t end, int32_t bound,
+WTZ_HD uint32_t wtz_scan_windows_rest(const wtz_zhit_t *rs, uint32_t dir, uint32_t beg, uint32_t end, int32_t bound,
 		wtz_vec<wtz_win_t> &wins, wtz_vec<wtz_zhit_t> &anchors, const wtz_winscratch_t &sc, uint32_t zsize, uint32_t kwin, uint32_t zovl, int32_t *max_e0, uint32_t n, unsigned long long pw0, uint64_t *KB){
 	const uint32_t lane = WTZ_LANE;
 	/* K = the LDS slice (K_LDS: the address space stays static, DS instructions), or the pool workspace of a scan that does not fit it: the same code, the
@@ -371,7 +355,7 @@ retry_scan:
 		for(uint32_t b0 = beg; b0 < end; b0 += WTZ_NLANES){      /* K in the ORIGINAL order again */
 			const uint32_t idx = b0 + lane;
 			bool keep = false; uint32_t o2 = 0;
-			if(idx < end){ const uint32_t o1 = rs[idx].o1; o2 = rs[idx].o2; keep = (((o1 ^ o2) >> 31) == dir) && ((int32_t)(o1 & 0x7FFFFFFFu) >= bound); }
+			if(idx < end){ const uint32_t o1 = rs[idx].o1; o2 = rs[idx].o2; keep = wtz_scan_keeps(o1, o2, dir, bound); }
 			uint32_t tot; const uint32_t pos = wtz_coop_rank(keep, &tot);
 			if(keep) K[m + pos] = ((uint64_t)(o2 & 0x7FFFFFFFu) << 32) | idx;
 			m += tot;
@@ -456,11 +440,7 @@ retry_scan:
 			}
 			WTZ_WAVE_SYNC();                                 /* EP of this chunk is read before the next chunk writes beside it */
 		}
-#ifdef WTZ_EXP_CNT_EMPTY
-		WTZ_PROF_ADD(19, pw3); pw4 = WTZ_PROF_T(); WTZ_PROF_CNT(23, n2 == 0 ? 1 : 0);      /* diagnostic build: scans whose sweep finds no window */
-#else
 		WTZ_PROF_ADD(19, pw3); pw4 = WTZ_PROF_T(); WTZ_PROF_CNT(23, n2);
-#endif
 		n2_all = n2;
 		if(had_tie && !exact){          /* (a): does a window end inside a tie group? */
 			uint32_t cut = 0;
@@ -704,8 +684,8 @@ WTZ_DN uint32_t wtz_scan_windows_rest_pool_chain(const wtz_zhit_t *rs, uint32_t 
 	return wtz_scan_windows_rest<false, true>(rs, dir, beg, end, bound, wins, anchors, sc, zsize, kwin, zovl, max_e0, n, pw0, KB);
 }
 
-template<bool ZBIG, bool CHAIN = false>
-WTZ_SCAN_FN uint32_t wtz_scan_windows_coop(const wtz_zhit_t *rs, uint32_t dir, uint32_t beg, uint32_t end, int32_t bound,
+template<bool CHAIN = false>
+WTZ_HD uint32_t wtz_scan_windows_coop(const wtz_zhit_t *rs, uint32_t dir, uint32_t beg, uint32_t end, int32_t bound,
 		wtz_vec<wtz_win_t> &wins, wtz_vec<wtz_zhit_t> &anchors, const wtz_winscratch_t &sc, uint32_t zsize, uint32_t kwin, uint32_t zovl, int32_t *max_e0){
 	const uint32_t lane = WTZ_LANE;
 	uint64_t *K = sc.lds;
@@ -715,55 +695,31 @@ WTZ_SCAN_FN uint32_t wtz_scan_windows_coop(const wtz_zhit_t *rs, uint32_t dir, u
 	const unsigned long long pw0 = WTZ_PROF_T(); (void)pw0;
 	/* ---- strand / bound filter (the prefix skip of hzm_aln.h:425-431 is the same predicate: off1 is non-decreasing) ---- */
 	constexpr uint32_t RC = 4;                         /* a range of up to RC matches per lane is read ONCE: count, early-exit bound and key fill run on the off2 values kept in registers */
-#ifndef WTZ_NO_SCAN_CACHE
 	/* ... and its ordering workspace (power of two >= 64 keys + two words per match + 2) fits the slice whatever the count turns out to be */
 	const bool cached = (K != NULL) && (end - beg <= WTZ_NLANES * RC) && (sc.lds_u64 >= (WTZ_NLANES * RC > 64u ? WTZ_NLANES * RC : 64u) + 2u * WTZ_NLANES * RC + 2u);
-#else
-	const bool cached = false;
-#endif
 	if(cached){
 		uint32_t q2[RC]; uint32_t kpm = 0;              /* off2 of this lane's matches; bit c: match c passes the strand / bound filter */
 		#pragma unroll
 		for(uint32_t c = 0; c < RC; c++){
 			const uint32_t idx = beg + c * WTZ_NLANES + lane;
 			q2[c] = 0;
-			if(idx < end){ const uint32_t o1 = rs[idx].o1, o2 = rs[idx].o2; q2[c] = o2 & 0x7FFFFFFFu; if((((o1 ^ o2) >> 31) == dir) && ((int32_t)(o1 & 0x7FFFFFFFu) >= bound)) kpm |= 1u << c; }
+			if(idx < end){ const uint32_t o1 = rs[idx].o1, o2 = rs[idx].o2; q2[c] = o2 & 0x7FFFFFFFu; if(wtz_scan_keeps(o1, o2, dir, bound)) kpm |= 1u << c; }
 		}
 		n = 0;
 		#pragma unroll
 		for(uint32_t c = 0; c < RC; c++) n += (uint32_t)__builtin_popcountll(wtz_coop_ballot((kpm >> c) & 1u));
 		if(n * zsize < zovl){ WTZ_PROF_ADD(12, pw0); WTZ_PROF_CNT(7, 1); return 0; }
-#ifndef WTZ_NO_SCAN_PRECHECK
-		{       /* the exact early exit described below, on the cached matches (their len2 is read here, by the scans that get this far) */
+		{       /* the exact early exit on the cached matches (their len2 is read here, by the scans that get this far) */
 			uint32_t mn = 0xFFFFFFFFu, mx = 0;
 			#pragma unroll
 			for(uint32_t c = 0; c < RC; c++) if((kpm >> c) & 1u){ mn = q2[c] < mn ? q2[c] : mn; mx = q2[c] > mx ? q2[c] : mx; }
 			mn = wtz_coop_min32(mn); mx = ~wtz_coop_min32(~mx);
-			const uint32_t bw = kwin >= 8 ? kwin / 8 : 1;
-			const uint32_t nadj = (kwin - 1) / bw + 2;      /* the bins are aligned to mn, not to the window: kwin - 1 columns starting anywhere inside a bin reach into one more */
-			const uint32_t nb = (mx - mn) / bw + 1 + nadj;
-			if(nb <= sc.lds_u64 * 2){
-				uint32_t *B = (uint32_t*)K;
-				for(uint32_t b = lane; b < nb; b += WTZ_NLANES) B[b] = 0;
-				WTZ_WAVE_SYNC();
+			const bool none = wtz_scan_cannot_open(mn, mx, [&](auto f){
 				#pragma unroll
-				for(uint32_t c = 0; c < RC; c++) if((kpm >> c) & 1u){
-					const uint32_t bin = (q2[c] - mn) / bw, l2 = rs[beg + c * WTZ_NLANES + lane].ll >> 16;
-#if defined(__HIP_DEVICE_COMPILE__)
-					atomicAdd(&B[bin], l2);
-#else
-					B[bin] += l2;
-#endif
-				}
-				WTZ_WAVE_SYNC();
-				uint32_t best = 0;
-				for(uint32_t b = lane; b + nadj <= nb; b += WTZ_NLANES){ uint32_t v = 0; for(uint32_t t = 0; t < nadj; t++) v += B[b + t]; best = v > best ? v : best; }
-				best = ~wtz_coop_min32(~best);
-				WTZ_WAVE_SYNC();
-				if(best < zovl){ WTZ_PROF_CNT(23, 0); WTZ_PROF_ADD(12, pw0); WTZ_PROF_CNT(7, 1); return 0; }
-			}
+				for(uint32_t c = 0; c < RC; c++) if((kpm >> c) & 1u) f(q2[c], rs[beg + c * WTZ_NLANES + lane].ll >> 16);
+			}, (uint32_t*)K, sc.lds_u64 * 2, kwin, zovl);
+			if(none){ WTZ_PROF_CNT(23, 0); WTZ_PROF_ADD(12, pw0); WTZ_PROF_CNT(7, 1); return 0; }
 		}
-#endif
 		uint32_t m = 0;
 		#pragma unroll
 		for(uint32_t c = 0; c < RC; c++){
@@ -778,64 +734,30 @@ WTZ_SCAN_FN uint32_t wtz_scan_windows_coop(const wtz_zhit_t *rs, uint32_t dir, u
 		for(uint32_t b0 = beg; b0 < end; b0 += WTZ_NLANES){
 			const uint32_t idx = b0 + lane;
 			bool keep = false; uint32_t o2 = 0;
-			if(idx < end){ const uint32_t o1 = rs[idx].o1; o2 = rs[idx].o2; keep = (((o1 ^ o2) >> 31) == dir) && ((int32_t)(o1 & 0x7FFFFFFFu) >= bound); }
+			if(idx < end){ const uint32_t o1 = rs[idx].o1; o2 = rs[idx].o2; keep = wtz_scan_keeps(o1, o2, dir, bound); }
 			uint32_t tot; const uint32_t pos = wtz_coop_rank(keep, &tot);
 			if(pass && keep) K[n + pos] = ((uint64_t)(o2 & 0x7FFFFFFFu) << 32) | idx;
 			n += tot;
 		}
 		if(pass) break;
 		if(n * zsize < zovl){ WTZ_PROF_ADD(12, pw0); WTZ_PROF_CNT(7, 1); return 0; }      /* profiler: 12 = time in scans that end before the ordering, 7 = how many */
-#ifndef WTZ_NO_SCAN_PRECHECK
-		/* ---- exact early exit (round 3): can the sweep of hzm_aln.h:451-483 reach `ol >= zovl` at all?  In off2 order the running overlap is
-		 * ol = sum of len2 over the in-window matches j..i minus the overlaps of neighbours (a match adds len2 minus its overlap with the one
-		 * before, an eviction takes len2 minus the overlap with the one behind; ends are monotone in off2 for the matches of one strand), so
-		 * ol <= sum of len2 over j..i, and the while loop keeps off2[i] - off2[j] < kwin: the in-window matches lie in nadj adjacent bins of
-		 * kwin / 8 columns (nine bins = 1.125 kwin: eight would miss a window that starts late in its first bin).  If no such run of bins holds zovl bases of matches, no window can open, n2 stays 0 and the scan returns 0 - without
-		 * the off2 ordering, the gather and the lane-0 sweep.  Tie order cannot matter: the bound is over sets. ---- */
 		if(K != NULL){
-			uint32_t mn = 0xFFFFFFFFu, mx = 0;
-			for(uint32_t b0 = beg; b0 < end; b0 += WTZ_NLANES){
-				const uint32_t idx = b0 + lane;
-				if(idx < end){ const uint32_t o1 = rs[idx].o1, o2 = rs[idx].o2; if((((o1 ^ o2) >> 31) == dir) && ((int32_t)(o1 & 0x7FFFFFFFu) >= bound)){ const uint32_t f = o2 & 0x7FFFFFFFu; mn = f < mn ? f : mn; mx = f > mx ? f : mx; } }
-			}
-			mn = wtz_coop_min32(mn); mx = ~wtz_coop_min32(~mx);
-			const uint32_t bw = kwin >= 8 ? kwin / 8 : 1;          /* bins of an eighth of the window: the in-window matches span < kwin columns = at most nadj adjacent bins */
-			const uint32_t nadj = (kwin - 1) / bw + 2;      /* the bins are aligned to mn, not to the window: kwin - 1 columns starting anywhere inside a bin reach into one more */
-			const uint32_t nb = (mx - mn) / bw + 1 + nadj;         /* nadj empty bins behind the last: every run of nadj bins starting at a used bin is inside the array */
-			if(nb <= sc.lds_u64 * 2){
-				uint32_t *B = (uint32_t*)K;
-				for(uint32_t b = lane; b < nb; b += WTZ_NLANES) B[b] = 0;
-				WTZ_WAVE_SYNC();
+			const auto each = [&](auto f){
 				for(uint32_t b0 = beg; b0 < end; b0 += WTZ_NLANES){
 					const uint32_t idx = b0 + lane;
-					if(idx < end){
-						const uint32_t o1 = rs[idx].o1, o2 = rs[idx].o2;
-						if((((o1 ^ o2) >> 31) == dir) && ((int32_t)(o1 & 0x7FFFFFFFu) >= bound)){
-							const uint32_t bin = ((o2 & 0x7FFFFFFFu) - mn) / bw, l2 = rs[idx].ll >> 16;
-#if defined(__HIP_DEVICE_COMPILE__)
-							atomicAdd(&B[bin], l2);
-#else
-							B[bin] += l2;
-#endif
-						}
-					}
+					if(idx < end){ const uint32_t o1 = rs[idx].o1, o2 = rs[idx].o2; if(wtz_scan_keeps(o1, o2, dir, bound)) f(o2 & 0x7FFFFFFFu, rs[idx].ll >> 16); }
 				}
-				WTZ_WAVE_SYNC();
-				uint32_t best = 0;
-				for(uint32_t b = lane; b + nadj <= nb; b += WTZ_NLANES){ uint32_t v = 0; for(uint32_t t = 0; t < nadj; t++) v += B[b + t]; best = v > best ? v : best; }
-				best = ~wtz_coop_min32(~best);
-				WTZ_WAVE_SYNC();                                  /* K is written again by the second pass */
-				if(best < zovl){ WTZ_PROF_CNT(23, 0); WTZ_PROF_ADD(12, pw0); WTZ_PROF_CNT(7, 1); return 0; }
-			}
+			};
+			uint32_t mn = 0xFFFFFFFFu, mx = 0;
+			each([&](uint32_t f, uint32_t){ mn = f < mn ? f : mn; mx = f > mx ? f : mx; });
+			mn = wtz_coop_min32(mn); mx = ~wtz_coop_min32(~mx);
+			if(wtz_scan_cannot_open(mn, mx, each, (uint32_t*)K, sc.lds_u64 * 2, kwin, zovl)){ WTZ_PROF_CNT(23, 0); WTZ_PROF_ADD(12, pw0); WTZ_PROF_CNT(7, 1); return 0; }
 		}
-#endif
 		uint32_t np0 = 64; while(np0 < n) np0 <<= 1;
 		if(K == NULL || np0 + 2 * n + 2 > sc.lds_u64){
 			/* does not fit the LDS slice (a few hundred matches of one strand inside one window: repeats): the same wave-parallel scan on a workspace in the pool.
 			 * (Round 3 ran these on lane 0 - a sort of thousands of matches by dependent memory accesses; the heaviest pair of a range took half of its launch.) */
-			if(!ZBIG){ sc.need_big = 1; *max_e0 = -0x7FFFFFFF; return 0; }
 			const uint32_t need = np0 + 2 * n + 2;
-#ifndef WTZ_PAIR_NO_POOL_SCAN
 			if(sc.big_u64 < need){
 				const uint32_t cap = need > 2 * sc.big_u64 ? need : 2 * sc.big_u64;
 				uint64_t pa = 0;
@@ -843,27 +765,21 @@ WTZ_SCAN_FN uint32_t wtz_scan_windows_coop(const wtz_zhit_t *rs, uint32_t dir, u
 				pa = wtz_coop_bcast64(pa);
 				if(pa){ sc.big = (uint64_t*)(uintptr_t)pa; sc.big_u64 = cap; }
 			}
-#endif
-#ifdef WTZ_PAIR_NO_POOL_SCAN
-			if(false){
-#else
 			if(sc.big_u64 >= need){
-#endif
 				uint64_t *KB = sc.big; uint32_t m = 0;
 				for(uint32_t b0 = beg; b0 < end; b0 += WTZ_NLANES){
 					const uint32_t idx = b0 + lane;
 					bool keep = false; uint32_t o2 = 0;
-					if(idx < end){ const uint32_t o1 = rs[idx].o1; o2 = rs[idx].o2; keep = (((o1 ^ o2) >> 31) == dir) && ((int32_t)(o1 & 0x7FFFFFFFu) >= bound); }
+					if(idx < end){ const uint32_t o1 = rs[idx].o1; o2 = rs[idx].o2; keep = wtz_scan_keeps(o1, o2, dir, bound); }
 					uint32_t tot; const uint32_t pos = wtz_coop_rank(keep, &tot);
 					if(keep) KB[m + pos] = ((uint64_t)(o2 & 0x7FFFFFFFu) << 32) | idx;
 					m += tot;
 				}
-				if constexpr(ZBIG){       /* a real call: its results come back in vector registers - say again that they are uniform */
-					const uint32_t r = CHAIN ? wtz_scan_windows_rest_pool_chain(rs, dir, beg, end, bound, wins, anchors, sc, zsize, kwin, zovl, max_e0, n, pw0, KB)
-					                         : wtz_scan_windows_rest_pool(rs, dir, beg, end, bound, wins, anchors, sc, zsize, kwin, zovl, max_e0, n, pw0, KB);
-					*max_e0 = (int32_t)wtz_coop_bcast32((uint32_t)*max_e0);
-					return wtz_coop_bcast32(r);
-				}
+				/* a real call: its results come back in vector registers - say again that they are uniform */
+				const uint32_t r = CHAIN ? wtz_scan_windows_rest_pool_chain(rs, dir, beg, end, bound, wins, anchors, sc, zsize, kwin, zovl, max_e0, n, pw0, KB)
+				                         : wtz_scan_windows_rest_pool(rs, dir, beg, end, bound, wins, anchors, sc, zsize, kwin, zovl, max_e0, n, pw0, KB);
+				*max_e0 = (int32_t)wtz_coop_bcast32((uint32_t)*max_e0);
+				return wtz_coop_bcast32(r);
 			} else {                                      /* no room in the pool either: wtz_pool_alloc has flagged the pool, the stage ends in WTZ_E_POOL and the range is redone in halves */
 				if(lane == 0) wins.bad = 1;
 				*max_e0 = -0x7FFFFFFF;
@@ -874,72 +790,9 @@ WTZ_SCAN_FN uint32_t wtz_scan_windows_coop(const wtz_zhit_t *rs, uint32_t dir, u
 	return wtz_scan_windows_rest<true, CHAIN>(rs, dir, beg, end, bound, wins, anchors, sc, zsize, kwin, zovl, max_e0, n, pw0, NULL);
 }
 
-template<bool ZBIG, bool CHAIN = false>
-WTZ_HD uint32_t wtz_merge_windows_coop(const wtz_zhit_t *rs, uint32_t n_rs, uint32_t dir, wtz_vec<wtz_win_t> &wins, wtz_vec<wtz_zhit_t> &anchors,
-		const wtz_winscratch_t &sc, uint32_t zsize, uint32_t kwin, uint32_t kstep, uint32_t zovl){
-	/* every value this loop branches on is the same in all lanes - say so (v_readfirstlane): without it the compiler keeps the cursors in vector registers and
-	 * runs each of the ~4 000 iterations per pair through exec-mask save / restore sequences (round 4's profile: this loop, not the scans, was 55 % of K_pair) */
-	n_rs = wtz_coop_bcast32(n_rs); dir = wtz_coop_bcast32(dir); zsize = wtz_coop_bcast32(zsize); kwin = wtz_coop_bcast32(kwin); kstep = wtz_coop_bcast32(kstep); zovl = wtz_coop_bcast32(zovl);
-	const uint32_t P_off1 = 0x1FFFFFu, P_len1 = 0x3FFu, lim = n_rs + 1;
-	uint32_t i, j, n, ol, ol2, lst, wlst, s, t, ret, o1, o2, ll;
-	uint32_t p_off1, p_len1, p0_off1, p0_len1, p1_off1, p1_len1;
-	int32_t nxt;
-	wtz_hitcur_t ci, cj; ci.base = cj.base = 0x80000000u; ci.o1 = ci.o2 = ci.ll = cj.o1 = cj.o2 = cj.ll = 0;
-	ol = 0; lst = 0; wlst = 0; ret = 0;
-	for(j = 0; j < n_rs; j++){ wtz_hitcur_get(cj, rs, lim, j, o1, o2, ll); if(((o1 ^ o2) >> 31) ^ dir) continue; break; }
-	if(j == n_rs) return 0;
-	wtz_hitcur_get(cj, rs, lim, j, o1, o2, ll);
-	p0_off1 = o1 & 0x7FFFFFFFu; p0_len1 = ll & 0xFFFFu;
-	p_off1 = p_len1 = 0;
-	for(i = j; i <= n_rs; i++){
-		if(i < n_rs){
-			wtz_hitcur_get(ci, rs, lim, i, o1, o2, ll);
-			if(((o1 ^ o2) >> 31) ^ dir) continue;
-			p_off1 = o1 & 0x7FFFFFFFu; p_len1 = ll & 0xFFFFu;
-		} else { p_off1 = P_off1; p_len1 = P_len1; }
-		if(p_off1 > p0_off1 + kwin){
-			if(ol >= zovl){
-				int32_t me0 = 0;
-				n = wtz_scan_windows_coop<ZBIG, CHAIN>(rs, dir, j, i, (int32_t)wlst, wins, anchors, sc, zsize, kwin, zovl, &me0);
-				if(!ZBIG && sc.need_big) return 0;
-				if(n){
-					if((int32_t)wlst < me0 + 20) wlst = (uint32_t)(me0 + 20);
-					ret += n;
-					p0_off1 = p_off1; p0_len1 = p_len1; ol = p_len1; lst = p_off1 + p_len1; j = i;
-				} else {
-					nxt = (int32_t)(p0_off1 + kstep);
-					while((int32_t)p0_off1 < nxt && j < i){
-						++j; wtz_hitcur_get(cj, rs, lim, j, o1, o2, ll); p1_off1 = o1 & 0x7FFFFFFFu; p1_len1 = ll & 0xFFFFu;
-						s = WTZ_MAX(p0_off1, p1_off1);
-						t = WTZ_MIN(p0_off1 + p0_len1, p1_off1 + p1_len1);
-						ol2 = s < t ? t - s : 0;
-						ol = ol + ol2 - p0_len1;
-						p0_off1 = p1_off1; p0_len1 = p1_len1;
-					}
-				}
-			}
-			if(p_off1 == P_off1) break;
-			while(p_off1 > p0_off1 + kwin){
-				++j; wtz_hitcur_get(cj, rs, lim, j, o1, o2, ll); p1_off1 = o1 & 0x7FFFFFFFu; p1_len1 = ll & 0xFFFFu;
-				s = WTZ_MAX(p0_off1, p1_off1);
-				t = WTZ_MIN(p0_off1 + p0_len1, p1_off1 + p1_len1);
-				ol2 = s < t ? t - s : 0;
-				ol = ol + ol2 - p0_len1;
-				p0_off1 = p1_off1; p0_len1 = p1_len1;
-			}
-		} else {
-			if(p_off1 >= lst) ol += p_len1;
-			else if((int32_t)(p_off1 + p_len1) > (int32_t)lst) ol += p_off1 + p_len1 - lst;
-			else continue;
-			lst = p_off1 + p_len1;
-		}
-	}
-	return ret;
-}
-
 /* ---------------------------------------------------------------------------------------------------------------------------------------------------
- * The window merge on the whole wavefront (round 5).  wtz_merge_windows_coop above is the reference's loop (hzm_aln.h:580-656) with every lane doing the same
- * scalar work: ~8 000 dependent steps per pair, ~40 scalar instructions each, through the ONE scalar unit the 16 waves of a CU share - three quarters of K_pair.
+ * The window merge on the whole wavefront (round 5).  The reference's loop (merge_paired_kmers_window, hzm_aln.h:580-656), run as it stands with every lane doing the
+ * same scalar work, is ~8 000 dependent steps per pair, ~40 scalar instructions each, through the ONE scalar unit the 16 waves of a CU share - three quarters of K_pair.
  * Between two window scans the loop is a function of tables that do not depend on its state:
  *   - the matches are in off1 order (both strands), so "match i lies beyond off1[j] + kwin" is  j < F[i]  with  F[i] = the first index whose off1 + kwin reaches
  *     off1[i]  (non-decreasing in i), and the `while` that moves the window start there is  j <- max(j, F[i]);  the start before step i is therefore the running
@@ -990,7 +843,7 @@ WTZ_HD void wtz_merge_prepare(const wtz_zhit_t *rs, uint32_t n_rs, const wtz_win
 	WTZ_WAVE_SYNC();
 }
 
-template<bool ZBIG, bool CHAIN = false>
+template<bool CHAIN = false>
 WTZ_HD uint32_t wtz_merge_windows_wave(const wtz_zhit_t *rs, uint32_t n_rs, uint32_t dir, wtz_vec<wtz_win_t> &wins, wtz_vec<wtz_zhit_t> &anchors,
 		const wtz_winscratch_t &sc, uint32_t zsize, uint32_t kwin, uint32_t kstep, uint32_t zovl){
 	n_rs = wtz_coop_bcast32(n_rs); dir = wtz_coop_bcast32(dir); zsize = wtz_coop_bcast32(zsize); kwin = wtz_coop_bcast32(kwin); kstep = wtz_coop_bcast32(kstep); zovl = wtz_coop_bcast32(zovl);
@@ -1035,8 +888,7 @@ WTZ_HD uint32_t wtz_merge_windows_wave(const wtz_zhit_t *rs, uint32_t n_rs, uint
 		bool taken = false;
 		if(ol >= zovl){
 			int32_t me0 = 0;
-			const uint32_t n = wtz_scan_windows_coop<ZBIG, CHAIN>(rs, dir, j, it, (int32_t)wlst, wins, anchors, sc, zsize, kwin, zovl, &me0);
-			if(!ZBIG && sc.need_big) return 0;
+			const uint32_t n = wtz_scan_windows_coop<CHAIN>(rs, dir, j, it, (int32_t)wlst, wins, anchors, sc, zsize, kwin, zovl, &me0);
 			if(n){
 				if((int32_t)wlst < me0 + 20) wlst = (uint32_t)(me0 + 20);
 				ret += n;
@@ -1064,8 +916,7 @@ WTZ_HD uint32_t wtz_merge_windows_wave(const wtz_zhit_t *rs, uint32_t n_rs, uint
 	/* the sentinel behind the last match (hzm_aln.h:589): one more scan when the window has enough in it; nothing after it is observable */
 	if(SENT_OFF > wtz_coop_bcast32(ZH_OFF1(rs[j])) + kwin && ol >= zovl){
 		int32_t me0 = 0;
-		const uint32_t n = wtz_scan_windows_coop<ZBIG, CHAIN>(rs, dir, j, n_rs, (int32_t)wlst, wins, anchors, sc, zsize, kwin, zovl, &me0);
-		if(!ZBIG && sc.need_big) return 0;
+		const uint32_t n = wtz_scan_windows_coop<CHAIN>(rs, dir, j, n_rs, (int32_t)wlst, wins, anchors, sc, zsize, kwin, zovl, &me0);
 		ret += n;
 	}
 	return ret;

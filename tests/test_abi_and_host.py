@@ -265,6 +265,22 @@ def test_word_level_base_packing(tmp_path):
     assert r.returncode == 0 and " 0 bad" in r.stdout, r.stdout + r.stderr
 
 
+def test_pair_task_order_is_a_bijection(tmp_path):
+    """wtz_pair_order, the block -> pair map of the K_pair / K_pair_dm launches (heavy pairs first through the list, then runs of xg pairs per XCD):
+    for xg in {0, 1, 3, 256}, nh in {0, 8, 9} and n_rest in {0, 1, 8 xg - 1, 8 xg, 8 xg + 1, 24 xg + 5} it is a bijection on [0, nh + n_rest), blocks
+    below nh map through the list unchanged and xg = 0 is the identity behind them (tests/emul/check_pair_order.cpp).  The image for xg = 3, nh = 0,
+    n_rest = 29 is the list the launches' own expression gave before the map had a name: t = b2 - r + (r & 7) * xg + (r >> 3), r = b2 % 24, on
+    the one full group, the identity on the five blocks behind it."""
+    exe = os.path.join(str(tmp_path), "check_pair_order")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-DWTZ_EMUL", "-Wno-unknown-pragmas", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "smartdenovo_amd", "csrc"),
+                    "-o", exe, os.path.join(ROOT, "tests", "emul", "check_pair_order.cpp")], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and " 0 bad" in r.stdout, r.stdout + r.stderr
+    assert re.search(r"^(\d+) cases", r.stdout, re.M).group(1) == "69"      # 4 x 3 x 6 minus the three n_rest = -1 of xg = 0
+    image = [int(x) for x in re.search(r"^image xg 3 nh 0 n_rest 29:(.*)$", r.stdout, re.M).group(1).split()]
+    assert image == [0, 3, 6, 9, 12, 15, 18, 21, 1, 4, 7, 10, 13, 16, 19, 22, 2, 5, 8, 11, 14, 17, 20, 23, 24, 25, 26, 27, 28]
+
+
 REF_EXE = os.path.join(ROOT, "oracle", "_ref", "wtzmo_ref")
 
 
