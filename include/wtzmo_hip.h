@@ -28,6 +28,7 @@
  *   wtz_pairs_seed_region <- the same with beg / end: query_single_read_seeds_by_region   hzm_aln.h:117-171, 1690-1693 (wtmsa.c:448-477, wtjnt)
  *   wtz_hzmaux_batch     <- align_hzmaux as one call per batch of (target, read, beg, end)  hzm_aln.h:1684-1775
  *   wtz_set_window_chaining <- HZM_FAST_WINDOW_KMER_CHAINING: the windows of a scan by the median diagonal or by chaining_hzmps   hzm_aln.h:36, 488, 544 (351-408)
+ *   wtz_set_gap_open     <- the I and D arguments of align_hzmaux (separate insertion / deletion opening costs)   hzm_aln.h:1684, wtmsa.c:633-634, wtcns.c:330, 340
  *
  * Everything returned is integer and bit-exact against `wtzmo -t 1`.  The order-dependent state of
  * the reference (closed pairs, contained-read masking, per-read coverage: wtzmo.c:806-822, 1065-1100,
@@ -220,6 +221,18 @@ int  wtz_pairs_seed_region(wtz_ctx_t *ctx, const uint32_t *qid, const uint32_t *
  * (the callers that set it are align_hzmaux's): WTZ_E_ARG otherwise, and the setting stays as it was. */
 int  wtz_set_window_chaining(wtz_ctx_t *ctx, int fast);
 
+/* The two gap-open costs of the device DPs, per context, as the reference's routines take them (negative or zero): I opens a run of query-only steps (op 1, the E
+ * state of kswx_extend_align_shift_core / kswx_extend_align_core: kswx.h:168, column 0 kswx.h:152, the leftover rows of the walk kswx.h:220-223), D a run of
+ * target-only steps (op 2, the F state: kswx.h:174, row 0 kswx.h:143, the leftover columns kswx.h:224-227); the band clamp takes max(I, D) (kswx.h:117), the gaps
+ * between windows call ksw_global2 with (-I, -E, -D, -E) (hzm_aln.h:1407), kswx_refine_alignment and the z-mer runs carry both.  wtmsa runs align_hzmaux with
+ * -2, -3 (wtmsa.c:633-634), wtcns with its -I / -D from the second iteration on (wtcns.c:330, 340).  The default is I = D = params.O - what wtzmo, wtgbo and wtext
+ * pass - and wtz_params_c is unchanged.  The setting holds for every later device DP that read params.O before: wtz_pairs_align (windows, gaps, end extensions,
+ * the refinement) and through it wtz_hzmaux_batch, wtz_extend_batch, wtz_test_dp, and the planners that size their launches; wtz_ctx_clone copies it.  The services
+ * that take their gap costs as arguments (wtz_local_batch, wtz_kext_batch, wtz_align_batch, wtz_alignx_batch, wtz_global_batch) and the dot-matrix engine do not
+ * read it.  With I != D the two one-wave register forms of K-sw3 run their split-cost instantiation (wtz_sw_frame.h); with I == D the code that ran before runs.
+ * A positive cost or one below -2^20 is WTZ_E_ARG and the setting stays as it was; it waits for the context's stream before it changes the device's block. */
+int  wtz_set_gap_open(wtz_ctx_t *ctx, int32_t I, int32_t D);
+
 /* Chain windows of the last wtz_pairs_seed, packed in (pair, strand) order: sum of nwin[] entries. */
 int  wtz_pairs_windows(wtz_ctx_t *ctx, wtz_winbox_t *wins, uint64_t n_wins);
 
@@ -395,8 +408,8 @@ int  wtz_pwtext_batch(wtz_ctx_t *ctx, const wtz_dp_problem_t *problems, const wt
  * records alone.  A cigar_cap smaller than the sum of the hits' cigar_len is WTZ_E_ARG, the text names the words needed and out[] is complete (offsets
  * included), so the caller can allocate and call again.
  * Needs params.aux_strand = 1 and the zmo engine (WTZ_E_ARG), and both reads of every pair in the z-index (wtz_zindex_build, or wtz_zindex_build_subset of the
- * targets AND the queries: the device reads a query's position-ordered z-mers from the index too) - WTZ_E_STATE otherwise.  params.O is the one gap-open
- * cost of every device DP: I = D = O.  WTZ_E_POOL: nothing was returned, use fewer pairs per call (the halving loop of the batch tools, ht_halving).
+ * targets AND the queries: the device reads a query's position-ordered z-mers from the index too) - WTZ_E_STATE otherwise.  The gap-open costs of every
+ * device DP are the context's pair (wtz_set_gap_open: align_hzmaux's I and D, e.g. -2, -3 as wtmsa passes them); until it is called both are params.O.  WTZ_E_POOL: nothing was returned, use fewer pairs per call (the halving loop of the batch tools, ht_halving).
  * The call ends the batch it ran, on success and on failure alike: the main pool goes back empty, wtz_pairs_windows / wtz_pairs_align need a new wtz_pairs_seed. */
 typedef struct { int32_t found, score, tb, te, qb, qe, aln, mat, mis, ins, del; uint32_t cigar_len; uint64_t cigar_off; } wtz_hzmaux_result_t;
 int  wtz_hzmaux_batch(wtz_ctx_t *ctx, const uint32_t *tid, const uint32_t *rid, const int32_t *beg, const int32_t *end, uint32_t n,

@@ -34,9 +34,17 @@
 #define WTZ_MAX(a,b) ((a) > (b) ? (a) : (b))
 #define WTZ_ABSDIFF(a,b) ((a) < (b) ? (b) - (a) : (a) - (b))
 
-/* ---------------- parameters: the public ABI struct (include/wtzmo_hip.h) ---------------- */
+/* ---------------- parameters: the public ABI struct (include/wtzmo_hip.h) and what the context adds to it ---------------- */
 #include "wtzmo_hip.h"
-typedef wtz_params_c wtz_params_t;
+/* the device's parameter block: the public fields as the caller gave them, then the two gap-open costs of the device DPs (wtz_set_gap_open; I = D = O until it is
+ * called).  I opens the E state (a run of query-only steps, op 1), D the F state (a run of target-only steps, op 2): kswx.h:168, 174.  Every device DP reads I / D;
+ * O stays what the caller passed and is read by nothing behind wtz_ctx_create. */
+#define WTZ_GAP_OPEN_MIN (-(1 << 20))      /* wtz_set_gap_open: params.O itself is not range-checked; beyond this the 32-bit sums of every form's envelope end */
+struct wtz_params_t : wtz_params_c {
+	int32_t I, D;
+	wtz_params_t() : wtz_params_c(), I(0), D(0) {}
+	wtz_params_t(const wtz_params_c &p) : wtz_params_c(p), I(p.O), D(p.O) {}
+};
 
 /* ---------------- record types ---------------- */
 /* z-mer match, 16 B like the reference's hzmp_t (hzm_aln.h:54-59): o1 = dir1<<31 | off1, o2 = dir2<<31 | off2,

@@ -329,10 +329,25 @@ extern "C" int wtz_ctx_clone(wtz_ctx_t *p, uint64_t pool_bytes, wtz_ctx_t **out)
 	int rc = wtz_ctx_create(p->device, &p->P, pool_bytes ? pool_bytes : p->pool_bytes, &c);
 	if(rc) return rc;
 	c->shares_indexes = true; c->window_chaining = p->window_chaining;
+	if(c->P.I != p->P.I || c->P.D != p->P.D){ rc = wtz_set_gap_open(c, p->P.I, p->P.D); if(rc){ wtz_ctx_destroy(c); return rc; } }
 	c->bits = p->bits; c->n_words = p->n_words; c->rdoff = p->rdoff; c->rdlen = p->rdlen; c->n_reads = p->n_reads; c->h_rdlen = p->h_rdlen;
 	c->ktab = p->ktab; c->kmask = p->kmask; c->kseeds = p->kseeds; c->n_kocc = p->n_kocc;
 	c->idx_beg = p->idx_beg; c->idx_end = p->idx_end; c->idx_len_sorted = p->idx_len_sorted;
 	for(int k = 0; k < 2; k++){ c->zs[k].zoff = p->zs[k].zoff; c->zs[k].n_z = p->zs[k].n_z; c->zs[k].Z = p->zs[k].Z; c->zs[k].have = p->zs[k].have; c->zs[k].sub = p->zs[k].sub; c->zs[k].members = p->zs[k].members; }
 	*out = c;
+	return WTZ_OK;
+}
+
+/* The gap-open costs of the device DPs, per context: I opens a run of query-only steps (the E state, kswx.h:168), D a run of target-only steps (the F state,
+ * kswx.h:174), as the reference's callers pass them (wtmsa.c:633-634: -2, -3).  Until it is called both are params.O. */
+extern "C" int wtz_set_gap_open(wtz_ctx_t *c, int32_t I, int32_t D){
+	if(!c) return wtz_fail(WTZ_E_ARG, "null context");
+	if(I > 0 || D > 0 || I < WTZ_GAP_OPEN_MIN || D < WTZ_GAP_OPEN_MIN) return wtz_fail(WTZ_E_ARG, "wtz_set_gap_open: I = %d, D = %d: costs are passed as the reference takes them, in [%d, 0]", I, D, WTZ_GAP_OPEN_MIN);
+	if(c->P.I == I && c->P.D == D) return WTZ_OK;
+	CTX_ENTER(c);
+	CHK(dev_sync());      /* nothing in flight reads the block while it changes */
+	wtz_params_t P = c->P; P.I = I; P.D = D;
+	CHK(dev_h2d(c->dP, &P, sizeof(wtz_params_t)));
+	c->P = P;
 	return WTZ_OK;
 }

@@ -2,15 +2,18 @@
  * wtz_lib_align.h — wtz_pairs_align and the stage runners under it: K-sw1 (lane pipeline, chained wave kernel), K-sw2 (lane pipeline,
  * wavefront kernel), K-sw3 (extension jobs, both ends fused on one wavefront), stitching.  Included by wtz_lib.cpp.
  */
+/* the context's two gap-open costs differ (wtz_set_gap_open): the K-sw3 register forms are launched in their split-cost instantiation (wtz_sw_frame.h), the
+ * lane DPs and the gap kernels in the instantiation that reads both costs; otherwise each runs the instantiation in which the two are one value, as before */
+static bool ext_split(const wtz_ctx *c){ return c->P.I != c->P.D; }
 #ifndef WTZ_EMUL
 /* upper bound of the transient-pool bytes one K-sw3 job takes (trace rows come 64 at a time; a row is the widest of the wave forms), its row bound and its band class */
-WTZ_HD uint64_t wtz_ext_trace_need(int32_t qlen, int32_t tlen, int32_t init, int32_t W, int32_t M, int32_t O, int32_t E, int32_t T, int32_t *ql_out, int32_t *ncol_out){
+WTZ_HD uint64_t wtz_ext_trace_need(int32_t qlen, int32_t tlen, int32_t init, int32_t W, int32_t M, int32_t I, int32_t D, int32_t E, int32_t T, int32_t *ql_out, int32_t *ncol_out){
 	if(ql_out) *ql_out = 0;
 	if(ncol_out) *ncol_out = 0;
 	if(qlen <= 0 || tlen <= 0) return 0;
 	if(init < 0) init = 0;
 	int32_t ql, tl, n_col;
-	wtz_ext_geometry(qlen, tlen, init, W, M, O, O, E, T, ql, tl, n_col);
+	wtz_ext_geometry(qlen, tlen, init, W, M, I, D, E, T, ql, tl, n_col);
 	if(ql_out) *ql_out = ql;
 	if(ncol_out) *ncol_out = n_col;
 	/* row bytes: the widest of the one-wave register forms (4-column steps), a 256-lane row (the layout of the removed four-wave kernels) and the LDS-ring kernel
@@ -27,8 +30,9 @@ WTZ_HD uint64_t wtz_ext_trace_need(int32_t qlen, int32_t tlen, int32_t init, int
 	return nb;
 }
 static uint64_t ext_trace_need(const wtz_ctx *c, int32_t qlen, int32_t tlen, int32_t init, int32_t W, int32_t *ql_out, int32_t *ncol_out){
-	return wtz_ext_trace_need(qlen, tlen, init, W, c->P.M, c->P.O, c->P.E, c->P.T, ql_out, ncol_out);
+	return wtz_ext_trace_need(qlen, tlen, init, W, c->P.M, c->P.I, c->P.D, c->P.E, c->P.T, ql_out, ncol_out);
 }
+#define WTZ_LAUNCH_SP(c, kernel, tw, ...) do { if(ext_split(c)) WTZ_LAUNCH((kernel<tw, true>), __VA_ARGS__); else WTZ_LAUNCH((kernel<tw, false>), __VA_ARGS__); } while(0)
 
 /* Both end extensions of every item of the stage on one wavefront per item (wtz_stitch_fused.h).  The items are ordered by the rows their two extensions can
  * run at most (longest first) and the launch is made only if the traces of ALL jobs fit the transient pool together (their geometry is known before any
@@ -43,13 +47,13 @@ static int run_stitch_fused(wtz_ctx *c, const wtz_env_t &V, const wtz_alnitem_t 
 	CHK(dev_alloc((void**)&d_k, (size_t)m * 8)); CHK(dev_alloc((void**)&d_order, (size_t)m * 4)); CHK(dev_alloc((void**)&d_acc, 24)); CHK(dev_set(d_acc, 0, 24));
 	if(c->sw.ext_pk) CHK(dev_alloc((void**)&d_open, ((size_t)m + 1) * 4));
 	{
-		const int32_t pM = c->P.M, pO = c->P.O, pE = c->P.E, pT = c->P.T, pW = -c->P.ew;
+		const int32_t pM = c->P.M, pI = c->P.I, pD = c->P.D, pE = c->P.E, pT = c->P.T, pW = -c->P.ew;
 		const bool use_pk = c->sw.ext_pk != 0; const wtz_params_t *dP = V.P;
 		CHK(wtz_launch<K_misc>(m, [=] WTZ_LAMBDA (uint64_t t){
 			const wtz_extjob_t &j = d_jl[t];
 			int32_t qa = 0, qb = 0;
-			unsigned long long nb = wtz_ext_trace_need(j.valid ? j.qlen : -1, j.tlen, 0, pW, pM, pO, pE, pT, &qa, (int32_t*)NULL);
-			nb += wtz_ext_trace_need(d_rgeo[2 * t], d_rgeo[2 * t + 1], 0, pW, pM, pO, pE, pT, &qb, (int32_t*)NULL);
+			unsigned long long nb = wtz_ext_trace_need(j.valid ? j.qlen : -1, j.tlen, 0, pW, pM, pI, pD, pE, pT, &qa, (int32_t*)NULL);
+			nb += wtz_ext_trace_need(d_rgeo[2 * t], d_rgeo[2 * t + 1], 0, pW, pM, pI, pD, pE, pT, &qb, (int32_t*)NULL);
 			const uint32_t rows = (uint32_t)qa + (uint32_t)qb;
 			/* which form takes the item (bit 32 of the key: the items of the 32-bit form end up behind those of the packed form, both longest-first): the packed
 			 * form needs both extensions inside its 16-bit window - the left one's init_score is known, the right one's is not (wtz_pk_window_range) */
@@ -57,7 +61,7 @@ static int run_stitch_fused(wtz_ctx *c, const wtz_env_t &V, const wtz_alnitem_t 
 			if(use_pk){
 				if(j.valid && j.qlen > 0 && j.tlen > 0){
 					int32_t W = pW, ql = 0, tl = 0, nc = 0, bias, ng, sh; const int32_t in0 = j.init_score < 0 ? 0 : j.init_score;
-					wtz_ext_geometry(j.qlen, j.tlen, in0, W, pM, pO, pO, pE, pT, ql, tl, nc);
+					wtz_ext_geometry(j.qlen, j.tlen, in0, W, pM, pI, pD, pE, pT, ql, tl, nc);
 					if(!wtz_pk_window(dP, in0, ql, tl, &bias, &ng, &sh)) to_fr = 1;
 				}
 				if(d_rgeo[2 * t] > 0 && d_rgeo[2 * t + 1] > 0){
@@ -69,7 +73,7 @@ static int run_stitch_fused(wtz_ctx *c, const wtz_env_t &V, const wtz_alnitem_t 
 					const wtz_gapres_t *gp = d_gaps + (it.regs - d_items[0].regs);
 					for(uint32_t k = st.first + 1; k < it.nwin; k++) if(it.regs[k].pass == 1) i_lo += (long long)gp[k].score + it.regs[k].x.score;
 					int32_t W = pW, ql = 0, tl = 0, nc = 0;
-					wtz_ext_geometry(d_rgeo[2 * t], d_rgeo[2 * t + 1], 0, W, pM, pO, pO, pE, pT, ql, tl, nc);
+					wtz_ext_geometry(d_rgeo[2 * t], d_rgeo[2 * t + 1], 0, W, pM, pI, pD, pE, pT, ql, tl, nc);
 					if(!wtz_pk_window_range(dP, ql, tl, i_lo, i_lo + gain)) to_fr = 1;
 				}
 			}
@@ -103,18 +107,18 @@ static int run_stitch_fused(wtz_ctx *c, const wtz_env_t &V, const wtz_alnitem_t 
 			CHK(dev_set(d_open, 0, 4));
 			if(n_fr){
 				HIPCHK(hipEventRecord(c->ev_side_fork, g_stream)); HIPCHK(hipStreamWaitEvent(c->stream_side, c->ev_side_fork, 0));
-				WTZ_LAUNCH((wtz_kernel_stitch_ext_fr<1032>), n_fr, 64, WTZ_WAVE_LDS_BYTES, c->stream_side, V, d_items, d_st, d_jl, d_jr, d_gaps, (const uint32_t*)d_order + (mg - n_fr), n_fr, 1u, 0u);
+				WTZ_LAUNCH_SP(c, wtz_kernel_stitch_ext_fr, 1032, n_fr, 64, WTZ_WAVE_LDS_BYTES, c->stream_side, V, d_items, d_st, d_jl, d_jr, d_gaps, (const uint32_t*)d_order + (mg - n_fr), n_fr, 1u, 0u);
 				HIPCHK(hipEventRecord(c->ev_side_join, c->stream_side));
 			}
 			const uint32_t n_pk = mg - n_fr;
 			if(n_pk){
-				WTZ_LAUNCH((wtz_kernel_stitch_ext_pk<1032>), n_pk, 64, WTZ_PK_LDS_BYTES(1032), g_stream, V, d_items, d_st, d_jl, d_jr, d_gaps, (const uint32_t*)d_order, n_pk, ng, g, d_open);
+				WTZ_LAUNCH_SP(c, wtz_kernel_stitch_ext_pk, 1032, n_pk, 64, WTZ_PK_LDS_BYTES(1032), g_stream, V, d_items, d_st, d_jl, d_jr, d_gaps, (const uint32_t*)d_order, n_pk, ng, g, d_open);
 			}
 			if(n_fr) HIPCHK(hipStreamWaitEvent(g_stream, c->ev_side_join, 0));
 			uint32_t n_open = 0; CHK(dev_d2h(&n_open, d_open, 4));
 			c->ext_open_total += n_open; c->ext_fr_total += n_fr;
-			if(n_open){ WTZ_LAUNCH((wtz_kernel_stitch_ext_fr<1032>), n_open, 64, WTZ_WAVE_LDS_BYTES, g_stream, V, d_items, d_st, d_jl, d_jr, d_gaps, (const uint32_t*)d_open + 1, n_open, 1u, 0u); }
-		} else WTZ_LAUNCH((wtz_kernel_stitch_ext_fr<1032>), mg, 64, WTZ_WAVE_LDS_BYTES, g_stream, V, d_items, d_st, d_jl, d_jr, d_gaps, (const uint32_t*)d_order, mg, ng, g);
+			if(n_open){ WTZ_LAUNCH_SP(c, wtz_kernel_stitch_ext_fr, 1032, n_open, 64, WTZ_WAVE_LDS_BYTES, g_stream, V, d_items, d_st, d_jl, d_jr, d_gaps, (const uint32_t*)d_open + 1, n_open, 1u, 0u); }
+		} else WTZ_LAUNCH_SP(c, wtz_kernel_stitch_ext_fr, 1032, mg, 64, WTZ_WAVE_LDS_BYTES, g_stream, V, d_items, d_st, d_jl, d_jr, d_gaps, (const uint32_t*)d_order, mg, ng, g);
 		ms_l += te.stop();
 		{
 			const int rc_t = tpool_check(c, "K-sw3 extension jobs (both ends on one wavefront)");
@@ -209,9 +213,9 @@ static int run_extjobs(wtz_ctx *c, const wtz_env_t &V, wtz_extjob_t *d_jobs, uin
 			/* one wavefront per job, longest first: the packed form, the 32-bit frame form (wtz_sw_frame.h) for what is outside the packed form's window, the
 			 * general kernel for what is outside the frame forms' envelope.  The forms these replaced are in the git history; CHANGELOG.md has their numbers. */
 			if(c->sw.ext_pk){      /* two 16-bit cells per register (wtz_sw_frame16.h); what is outside its window stays open for the 32-bit form */
-				WTZ_LAUNCH((wtz_kernel_extjobs_pk<1032>), g1 - g0, 64, 0, g_stream, d_jobs, (const uint32_t*)d_order + g0, g1 - g0, V.P, V.pool, V.pool + 1);
+				WTZ_LAUNCH_SP(c, wtz_kernel_extjobs_pk, 1032, g1 - g0, 64, 0, g_stream, d_jobs, (const uint32_t*)d_order + g0, g1 - g0, V.P, V.pool, V.pool + 1);
 			}
-			WTZ_LAUNCH((wtz_kernel_extjobs_fr<1032>), g1 - g0, 64, 0, g_stream, d_jobs, (const uint32_t*)d_order + g0, g1 - g0, V.P, V.pool, V.pool + 1);
+			WTZ_LAUNCH_SP(c, wtz_kernel_extjobs_fr, 1032, g1 - g0, 64, 0, g_stream, d_jobs, (const uint32_t*)d_order + g0, g1 - g0, V.P, V.pool, V.pool + 1);
 			WTZ_LAUNCH((wtz_kernel_extjobs<2048, 1032>), g1 - g0, 64, 0, g_stream, d_jobs, (const uint32_t*)d_order + g0, g1 - g0, V.P, V.pool, V.pool + 1);     /* whatever the frame forms left */
 			if(g1 < m || n_groups){ CHK(dev_sync()); CHK(tpool_check(c, "K-sw3 extension jobs")); }
 			g0 = g1; n_groups++;
@@ -324,7 +328,8 @@ static int run_winalign_lane(wtz_ctx *c, const wtz_env_t &V, const wtz_wintask_t
 		wtz_lclass_t L; const uint32_t wv = lane_classes(ccnt, &L);
 		uint64_t *d_wtr = NULL; uint32_t *d_wrm = NULL;
 		CHK(dev_alloc((void**)&d_wtr, ((size_t)wv + 1) * 8)); CHK(dev_alloc((void**)&d_wrm, ((size_t)wv + 1) * 4)); CHK(dev_set(d_wtr, 0, ((size_t)wv + 1) * 8));
-		if(wv) CHK(wtz_launch_coop<K_ldp>(wv, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_ldp_all((uint32_t)t, L, V, d_wt, d_items, d_ord, pp, rs, d_wtr, d_wrm); }, 0));
+		if(wv && ext_split(c)) CHK(wtz_launch_coop<K_ldp>(wv, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_ldp_all<true>((uint32_t)t, L, V, d_wt, d_items, d_ord, pp, rs, d_wtr, d_wrm); }, 0));
+		else if(wv) CHK(wtz_launch_coop<K_ldp>(wv, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_ldp_all<false>((uint32_t)t, L, V, d_wt, d_items, d_ord, pp, rs, d_wtr, d_wrm); }, 0));
 		lap(4);
 		if(wv) CHK(wtz_launch_coop<K_ltb>(wv, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_ltb_all((uint32_t)t, L, V, d_wt, d_items, d_ord, pp, ro, rn, rs, d_wtr, d_wrm); }, 0));
 		lap(6);
@@ -372,7 +377,8 @@ static int run_gap_lane(wtz_ctx *c, const wtz_env_t &V, const wtz_wintask_t *d_w
 		uint64_t *d_wtr = NULL; uint32_t *d_wrm = NULL; wtz_lres_t *d_res = NULL;
 		CHK(dev_alloc((void**)&d_wtr, ((size_t)wv + 1) * 8)); CHK(dev_alloc((void**)&d_wrm, ((size_t)wv + 1) * 4)); CHK(dev_set(d_wtr, 0, ((size_t)wv + 1) * 8));
 		CHK(pool_alloc_host(c, 0, ((size_t)nwt + 1) * sizeof(wtz_lres_t), (void**)&d_res)); CHK(dev_set(d_res, 0, ((size_t)nwt + 1) * sizeof(wtz_lres_t)));
-		if(wv) CHK(wtz_launch_coop<K_gdp>(wv, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_gdp_all((uint32_t)t, L, V, d_wt, d_items, d_ord, gp, d_res, d_wtr, d_wrm); }, 0));
+		if(wv && ext_split(c)) CHK(wtz_launch_coop<K_gdp>(wv, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_gdp_all<true>((uint32_t)t, L, V, d_wt, d_items, d_ord, gp, d_res, d_wtr, d_wrm); }, 0));
+		else if(wv) CHK(wtz_launch_coop<K_gdp>(wv, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_gdp_all<false>((uint32_t)t, L, V, d_wt, d_items, d_ord, gp, d_res, d_wtr, d_wrm); }, 0));
 		if(wv) CHK(wtz_launch_coop<K_gtb>(wv, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_gtb_all((uint32_t)t, L, V, d_wt, d_items, d_ord, gp, ro, rn, d_res, d_gaps, dn, d_wtr, d_wrm); }, 0));
 		CHK(wtz_launch<K_glist>(nwt, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_glist((uint32_t)t, dn, d_list); }));
 	}
@@ -435,12 +441,14 @@ static int compare_lane_with_chained(const wtz_reg_t *ra, const wtz_reg_t *rb, u
  * redone by the LDS-ring wave DP with 8192-column rings, 72 KB of LDS per wave.  Launches on the calling thread's current stream. */
 static int run_gap_wave(wtz_ctx *c, const wtz_env_t &V, const wtz_wintask_t *d_wt, const wtz_alnitem_t *d_items, wtz_gapres_t *d_gaps, const uint32_t *d_glist, uint32_t n_glist, uint64_t nwt){
 #ifdef WTZ_EMUL
-	(void)c; (void)nwt;
+	(void)nwt;      /* the emulation keeps the one instantiation that reads both costs */
+	(void)c;
 	return wtz_launch_coop<K_gap>(n_glist, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_gap((uint32_t)t, V, d_wt, d_items, d_gaps, (uint32_t*)NULL, (const uint32_t*)d_glist); }, WTZ_GAP_LDS_BYTES);
 #else
 	uint32_t *d_defer = NULL, n_def = 0; CHK(dev_alloc((void**)&d_defer, (size_t)(nwt + 1) * 4)); CHK(dev_set(d_defer, 0, 4));
 	STAGE(c, "K_gap");
-	CHK(wtz_launch_coop<K_gap>(n_glist, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_gap((uint32_t)t, V, d_wt, d_items, d_gaps, d_defer, (const uint32_t*)d_glist, 0u); }, WTZ_GAP_LDS_BYTES));
+	if(ext_split(c)) CHK(wtz_launch_coop<K_gap>(n_glist, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_gap<true>((uint32_t)t, V, d_wt, d_items, d_gaps, d_defer, (const uint32_t*)d_glist, 0u); }, WTZ_GAP_LDS_BYTES));
+	else CHK(wtz_launch_coop<K_gap>(n_glist, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_gap<false>((uint32_t)t, V, d_wt, d_items, d_gaps, d_defer, (const uint32_t*)d_glist, 0u); }, WTZ_GAP_LDS_BYTES));
 	CHK(dev_d2h(&n_def, d_defer, 4));
 	if(n_def) CHK(wtz_launch_coop<K_gap_wide>(n_def, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_gap((uint32_t)t, V, d_wt, d_items, d_gaps, NULL, d_defer, (uint32_t)WTZ_GAP_WIDE_LDS_BYTES); }, WTZ_GAP_WIDE_LDS_BYTES));
 	if(c->sw.profile){ CHK(dev_sync()); fprintf(stderr, "[gap-profile] %llu window slots, %u wide gaps redone with 72 KB of LDS\n", (unsigned long long)nwt, n_def); }

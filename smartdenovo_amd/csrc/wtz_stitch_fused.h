@@ -21,16 +21,17 @@
 #ifdef __HIPCC__
 /* the extension as a function of its own: its 250 registers are allocated for it alone, and what the kernel keeps across the call (the item, the side) is saved
  * once per job at the call, not spilled inside the row loop */
-template<int TW>
+template<int TW, bool SP>
 __device__ __attribute__((noinline)) bool wtz_extjob_run_fr_call(wtz_extjob_t *job, const wtz_params_t *Pm, wtz_pool_t *pool, wtz_pool_t *tpool){
 	__shared__ uint64_t stb[TW];      /* declared here, not passed in: the row loop reads it with LDS instructions, not through a generic pointer */
-	return wtz_extjob_run_fr<TW>(job, Pm, pool, tpool, stb);
+	return wtz_extjob_run_fr<TW, SP>(job, Pm, pool, tpool, stb);
 }
 template<int TW>
 __device__ __attribute__((noinline)) void wtz_stitch_mid_call(uint32_t t, const wtz_env_t *V, const wtz_alnitem_t *items, wtz_stitch_state_t *sts, const wtz_extjob_t *jobsL, wtz_extjob_t *jobsR, const wtz_gapres_t *gaps){
 	wtz_task_stitch_mid(t, *V, items, sts, jobsL, jobsR, gaps, true);
 }
-template<int TW>
+/* SP: the split-cost instantiation of the extensions (wtz_set_gap_open with I != D; wtz_sw_frame.h), chosen per launch */
+template<int TW, bool SP = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WTZ_OCC_EXTFR, 8))) wtz_kernel_stitch_ext_fr(const wtz_env_t V, const wtz_alnitem_t *items, wtz_stitch_state_t *sts,
 		wtz_extjob_t *jobsL, wtz_extjob_t *jobsR, const wtz_gapres_t *gaps, const uint32_t *order, uint32_t n, uint32_t stride, uint32_t first){
 	const uint32_t b = blockIdx.x;
@@ -42,7 +43,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WTZ_OCC
 			wtz_stitch_mid_call<TW>(t, &V, items, sts, jobsL, jobsR, gaps);
 			__threadfence_block();      /* lane 0 wrote the right job; the whole wave reads it */
 		}
-		if(!wtz_extjob_run_fr_call<TW>(side ? &jobsR[t] : &jobsL[t], V.P, V.pool, V.pool + 1)) return;
+		if(!wtz_extjob_run_fr_call<TW, SP>(side ? &jobsR[t] : &jobsL[t], V.P, V.pool, V.pool + 1)) return;
 		__threadfence_block();          /* lane 0 wrote the result and the operation list the join reads */
 	}
 }
@@ -54,13 +55,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WTZ_OCC
  * this kernel alone: two wavefronts per SIMD instead of three, measured as the same residency as the 32-bit form: SQ_WAVE_CYCLES / SQ_BUSY_CYCLES).  Inlined, the
  * three-wave budget holds for everything; what it costs is two or three spilled values per row of the widest class. */
 #define WTZ_PK_LDS_BYTES(TW) ((TW) * 8 + 64)
-template<int TW>
+template<int TW, bool SP>
 __device__ __attribute__((always_inline)) inline bool wtz_extjob_run_pk_call(wtz_extjob_t *job, const wtz_params_t *Pm, wtz_pool_t *pool, wtz_pool_t *tpool){
 	/* the wave's dynamic LDS slice (the join between the extensions uses its first WTZ_WAVE_LDS_BYTES while no extension runs): WTZ_PK_LDS_BYTES per wave instead of
 	 * a static array beside the slice - at 16 KB per wave a CU holds nine waves, and this kernel is built for twelve and more */
-	return wtz_extjob_run_pk<TW>(job, Pm, pool, tpool, (uint64_t*)wtz_wave_scratch());
+	return wtz_extjob_run_pk<TW, SP>(job, Pm, pool, tpool, (uint64_t*)wtz_wave_scratch());
 }
-template<int TW>
+template<int TW, bool SP = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WTZ_OCC_EXTPK, 8))) wtz_kernel_stitch_ext_pk(const wtz_env_t V, const wtz_alnitem_t *items, wtz_stitch_state_t *sts,
 		wtz_extjob_t *jobsL, wtz_extjob_t *jobsR, const wtz_gapres_t *gaps, const uint32_t *order, uint32_t n, uint32_t stride, uint32_t first, uint32_t *open){
 	const uint32_t b = blockIdx.x;
@@ -72,7 +73,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WTZ_OCC
 			wtz_task_stitch_mid(t, V, items, sts, jobsL, jobsR, gaps, true);
 			__threadfence_block();
 		}
-		if(!wtz_extjob_run_pk_call<TW>(side ? &jobsR[t] : &jobsL[t], V.P, V.pool, V.pool + 1)){
+		if(!wtz_extjob_run_pk_call<TW, SP>(side ? &jobsR[t] : &jobsL[t], V.P, V.pool, V.pool + 1)){
 			if((threadIdx.x & 63u) == 0){ const uint32_t k = atomicAdd(&open[0], 1u); open[1 + k] = t; }
 			return;
 		}

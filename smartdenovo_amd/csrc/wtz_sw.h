@@ -312,7 +312,7 @@ struct wtz_readview { const uint64_t *bits; uint64_t off; uint32_t len; uint32_t
 WTZ_HD wtz_aln_t wtz_align_window(const wtz_readview &pb1, const wtz_readview &pb2, const wtz_win_t &win, const wtz_zhit_t *anchors,
 		wtz_cigar_t &cigar, wtz_swmem_t &mem, wtz_cigar_t &tmp, const wtz_params_t *P){
 	wtz_aln_t x, y; memset(&x, 0, sizeof x);
-	const int32_t M = P->M, X = P->X, I = P->O, D = P->O, E = P->E, T = P->T;
+	const int32_t M = P->M, X = P->X, I = P->I, D = P->D, E = P->E, T = P->T;
 	for(uint32_t i = win.anchors[0]; i < win.anchors[1]; i++){
 		const wtz_zhit_t p = anchors[i];
 		const int32_t off1 = (int32_t)ZH_OFF1(p), off2 = (int32_t)ZH_OFF2(p);

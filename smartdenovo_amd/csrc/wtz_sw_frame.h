@@ -11,8 +11,10 @@
  *     m~ = G(i-1,j-1) + s - 2E            E~' = max(E~, m~ + I)            F~' = max(F~, m~ + D)          H~ = max(m~, E~, F~)
  * gap extension costs nothing (a vertical / horizontal step changes i+j by one, which is exactly the E the reference adds), the four
  * decisions of the trace byte are frame-invariant (every comparison is between values of ONE cell), the lane's F aggregate is a plain
- * maximum and the carry-in a plain prefix maximum.  I == D in every caller (wtzmo / wtgbo / wtext pass O for both), so t = m~ + O
- * serves both gap states.  The band start's move (S = 0, 1, 2) is folded into WHICH register a cell reads (three row bodies,
+ * maximum and the carry-in a plain prefix maximum.  I == D in the product (wtzmo / wtgbo / wtext pass O for both), so t = m~ + O
+ * serves both gap states there: that is the instantiation SP = false of everything below, unchanged.  After wtz_set_gap_open(I != D) - align_hzmaux as wtmsa
+ * and wtcns run it - the launches take SP = true: two open terms per cell (m~ + I feeds E~, m~ + D feeds F~), the lane's F aggregate and carry-in with D, row 0
+ * with D (kswx.h:143) and the band-start cell of a row with jb == 0 with I (kswx.h:152); one more VALU add per cell, nothing else moves.  The band start's move (S = 0, 1, 2) is folded into WHICH register a cell reads (three row bodies,
  * in-place register updates in an order that never overwrites an unread input): no moves.  The cells right of the band end are left
  * as they fall (they only feed cells further right); what the reference guarantees about them is restored where it can be observed:
  *   - the three register slots a LATER row can read (H at column je, E at je and je+1: the band end moves by at most 2 per row) are
@@ -56,9 +58,10 @@ WTZ_D void wtz_uniform_switch(const int32_t k, F &&f){
 	else { constexpr int MID = (LO + HI) / 2; if(k < MID) wtz_uniform_switch<LO, MID>(k, f); else wtz_uniform_switch<MID, HI>(k, f); }
 }
 
-template<int C, int S>
+template<int C, int S, bool SP>
 WTZ_D void wtz_fr_row(int32_t (&hv)[C], int32_t (&ev)[C], uint32_t (&zw)[(C + 3) / 4], const uint32_t eq_lo, const uint32_t eq_hi, const int lane,
-		const int32_t bnd, const int32_t SF, const int32_t MX, const int32_t Xp, const int32_t O, const int32_t (&ck)[C], int32_t &lkey){
+		const int32_t bnd, const int32_t SF, const int32_t MX, const int32_t Xp, const int32_t O, const int32_t D, const int32_t (&ck)[C], int32_t &lkey){
+	/* O: the opening cost of the E state (I), and with SP = false of both states; D: that of the F state, read with SP = true only */
 	/* ---- pass 1: m~ into hv[] in place (hv[k] <- f(old hv[k + S - 1])), the lane's F aggregate ---- */
 	int32_t agg = (int32_t)0x80000000;
 	if constexpr(S == 0){
@@ -92,7 +95,7 @@ WTZ_D void wtz_fr_row(int32_t (&hv)[C], int32_t (&ev)[C], uint32_t (&zw)[(C + 3)
 	 * left, floored by the frame image SF of the reference's f = -10000 at the band start ---- */
 	int32_t f;
 	{
-		const int32_t pm = wtz_wave_max_scan_excl(agg + O, SF);
+		const int32_t pm = wtz_wave_max_scan_excl(agg + (SP ? D : O), SF);
 		f = pm > SF ? pm : SF;
 	}
 	/* E~ of the cells: ev[k + S] of the old frame */
@@ -116,8 +119,9 @@ WTZ_D void wtz_fr_row(int32_t (&hv)[C], int32_t (&ev)[C], uint32_t (&zw)[(C + 3)
 		const int32_t t = m + O;
 		d = __builtin_amdgcn_alignbit(d, (uint32_t)(t - e), 31);                /* E extended: e + E > m + I + E */
 		const int32_t en = e > t ? e : t;
-		d = __builtin_amdgcn_alignbit(d, (uint32_t)(t - f), 31);                /* F extended */
-		f = f > t ? f : t;
+		const int32_t tf = SP ? m + D : t;                                       /* kswx.h:174: the F state opens with D */
+		d = __builtin_amdgcn_alignbit(d, (uint32_t)(tf - f), 31);               /* F extended */
+		f = f > tf ? f : tf;
 		hv[k] = h; ev[k] = en;                                                   /* no "bases equal" bit in this form's trace byte: mat / mis follow from the score (wtz_shift_traceback) */
 		const int32_t kk = (int32_t)(((uint32_t)h << 11) + (uint32_t)ck[k]);
 		key = kk > key ? kk : key;
@@ -127,9 +131,9 @@ WTZ_D void wtz_fr_row(int32_t (&hv)[C], int32_t (&ev)[C], uint32_t (&zw)[(C + 3)
 	lkey = key;
 }
 
-template<int C>
+template<int C, bool SP>
 WTZ_D wtz_aln_t wtz_extend_shift_fr(int32_t qlen, const wtz_seq_packed &query, int32_t tlen, const wtz_seq_packed &target, int32_t init_score,
-		int32_t ql, int32_t tl, int32_t W, int32_t M, int32_t X, int32_t O, int32_t E, int32_t T,
+		int32_t ql, int32_t tl, int32_t W, int32_t M, int32_t X, int32_t O, int32_t Dc, int32_t E, int32_t T,
 		uint64_t *tb, wtz_trace_t &tr, wtz_pool_t *pool, wtz_cigar_t &cigars, unsigned long long *cells, bool *ok, bool *consistent){
 	const int lane = (int)(threadIdx.x & 63);
 	wtz_aln_t x; memset(&x, 0, sizeof x);
@@ -141,6 +145,9 @@ WTZ_D wtz_aln_t wtz_extend_shift_fr(int32_t qlen, const wtz_seq_packed &query, i
 	qlen = __builtin_amdgcn_readfirstlane(qlen); tlen = __builtin_amdgcn_readfirstlane(tlen); init_score = __builtin_amdgcn_readfirstlane(init_score);
 	ql = __builtin_amdgcn_readfirstlane(ql); tl = __builtin_amdgcn_readfirstlane(tl); W = __builtin_amdgcn_readfirstlane(W);
 	M = __builtin_amdgcn_readfirstlane(M); X = __builtin_amdgcn_readfirstlane(X); O = __builtin_amdgcn_readfirstlane(O); E = __builtin_amdgcn_readfirstlane(E); T = __builtin_amdgcn_readfirstlane(T);
+	/* O = I, the cost of the E state and of column -1; D = the cost of the F state and of row -1 (SP = false: the same value, the same register) */
+	int32_t D = O;
+	if constexpr(SP) D = __builtin_amdgcn_readfirstlane(Dc);
 	constexpr int C4 = (C + 3) / 4;
 	const uint32_t zrow = (uint32_t)C4 * 256u;
 	if(!wtz_trace_prepare(tr, pool, zrow, ql, true)){ *ok = false; return x; }
@@ -163,7 +170,7 @@ WTZ_D wtz_aln_t wtz_extend_shift_fr(int32_t qlen, const wtz_seq_packed &query, i
 	#pragma unroll
 	for(int p = 0; p < C; p++){
 		const int32_t c = colrel0 + p - 1;
-		const int32_t hr = (c < 0) ? init_score : init_score + O + E * (c + 1);
+		const int32_t hr = (c < 0) ? init_score : init_score + D + E * (c + 1);
 		hv[p] = hr - (c - 1) * E;             /* G(-1,c) = H - (i+j)E with i = -1 */
 		ev[p] = -10000 - c * E;               /* E~(0,c) */
 	}
@@ -224,9 +231,9 @@ WTZ_D wtz_aln_t wtz_extend_shift_fr(int32_t qlen, const wtz_seq_packed &query, i
 		const int32_t bnd = ((jb == 0) ? init_score + O + E * i : -10000) - (i + jb - 2) * E;
 		const int32_t SF = -10000 - (i + jb) * E;
 		uint32_t zw[C4]; int32_t key;
-		if(s == 1)      wtz_fr_row<C, 1>(hv, ev, zw, eq_lo, eq_hi, lane, bnd, SF, MX, Xp, O, ck, key);
-		else if(s == 0) wtz_fr_row<C, 0>(hv, ev, zw, eq_lo, eq_hi, lane, bnd, SF, MX, Xp, O, ck, key);
-		else            wtz_fr_row<C, 2>(hv, ev, zw, eq_lo, eq_hi, lane, bnd, SF, MX, Xp, O, ck, key);
+		if(s == 1)      wtz_fr_row<C, 1, SP>(hv, ev, zw, eq_lo, eq_hi, lane, bnd, SF, MX, Xp, O, D, ck, key);
+		else if(s == 0) wtz_fr_row<C, 0, SP>(hv, ev, zw, eq_lo, eq_hi, lane, bnd, SF, MX, Xp, O, D, ck, key);
+		else            wtz_fr_row<C, 2, SP>(hv, ev, zw, eq_lo, eq_hi, lane, bnd, SF, MX, Xp, O, D, ck, key);
 		const int32_t nvt = je - jb;                       /* band-relative column of the first cell beyond the band end */
 		/* ---- row maximum and its FIRST arg-max (kswx.h:172) ---- */
 		{
@@ -316,26 +323,27 @@ WTZ_D wtz_aln_t wtz_extend_shift_fr(int32_t qlen, const wtz_seq_packed &query, i
 	if(gmax > 0 && gmax >= mx + T){ x.score = gmax; x.qe = gi; x.te = gj; }
 	else { x.score = mx; x.qe = mi; x.te = mj; }
 	__threadfence_block();
-	const wtz_tb_score sc = { M, X, O, E, init_score };
-	if(!wtz_shift_traceback<C, 64>(x, zchunk, zb, zrow, tb, cigars, &sc)) *ok = false, *consistent = false;
+	const wtz_tb_score sc = { M, X, O, D, E, init_score };
+	if(!wtz_shift_traceback<C, 64, SP>(x, zchunk, zb, zrow, tb, cigars, &sc)) *ok = false, *consistent = false;
 	return wtz_bcast_aln(x);
 }
 
 /* one K-sw3 job on the calling wavefront in the frame form; false = the job is outside the envelope (or its counts did not follow from the score) and stays
  * open for the general kernel (wtz_kernel_extjobs).  stb: TW 64-bit words of LDS of this wave. */
-template<int TW>
+template<int TW, bool SP>
 WTZ_D bool wtz_extjob_run_fr(wtz_extjob_t *job, const wtz_params_t *Pm, wtz_pool_t *pool, wtz_pool_t *tpool, uint64_t *stb){
 	if(!job->valid || job->done) return true;
 	const int lane = (int)(threadIdx.x & 63);
 	if(job->qlen <= 0 || job->tlen <= 0) return false;
 	const int32_t init_score = job->init_score < 0 ? 0 : job->init_score;
 	int32_t W = job->W, ql, tl, n_col;
-	wtz_ext_geometry(job->qlen, job->tlen, init_score, W, Pm->M, Pm->O, Pm->O, Pm->E, Pm->T, ql, tl, n_col);
+	const int32_t pI = Pm->I, pD = SP ? Pm->D : pI;
+	wtz_ext_geometry(job->qlen, job->tlen, init_score, W, Pm->M, pI, pD, Pm->E, Pm->T, ql, tl, n_col);
 	const int32_t Cw = (n_col + 63) / 64;
 	if(Cw > 32 || (tl + 63) / 32 + 1 > TW || (ql + 63) / 64 > WTZ_TRACE_MAXCHUNK) return false;
 	{
 		/* every value of the DP, its frame image and the -10000 family stay below 2^20 in magnitude */
-		const long long aE = Pm->E < 0 ? -(long long)Pm->E : (long long)Pm->E, aX = Pm->X < 0 ? -(long long)Pm->X : (long long)Pm->X, aO = Pm->O < 0 ? -(long long)Pm->O : (long long)Pm->O;
+		const long long aE = Pm->E < 0 ? -(long long)Pm->E : (long long)Pm->E, aX = Pm->X < 0 ? -(long long)Pm->X : (long long)Pm->X, pO = pI < pD ? pI : pD, aO = pO < 0 ? -(long long)pO : (long long)pO;      /* the larger of the two magnitudes (costs are <= 0) */
 		const long long span = (long long)ql + tl + 4;
 		if((long long)init_score + (long long)(Pm->M > 0 ? Pm->M : -Pm->M) * (ql < tl ? ql : tl) + span * aE + 10000 + aX + aO + 16 >= (1 << 20)) return false;
 		if(aE > 255 || Pm->M == Pm->X) return false;
@@ -345,7 +353,7 @@ WTZ_D bool wtz_extjob_run_fr(wtz_extjob_t *job, const wtz_params_t *Pm, wtz_pool
 	if(lane == 0) cg.init(pool, (uint32_t)ql / 2u + 16u);
 	unsigned long long cells = 0; bool ok = true, consistent = true;
 	wtz_aln_t x;
-#define WTZ_EXTFR_CASE(CM) x = wtz_extend_shift_fr<CM>(job->qlen, job->q, job->tlen, job->t, job->init_score, ql, tl, W, Pm->M, Pm->X, Pm->O, Pm->E, Pm->T, stb, tr, tpool, cg, &cells, &ok, &consistent)
+#define WTZ_EXTFR_CASE(CM) x = wtz_extend_shift_fr<CM, SP>(job->qlen, job->q, job->tlen, job->t, job->init_score, ql, tl, W, Pm->M, Pm->X, pI, pD, Pm->E, Pm->T, stb, tr, tpool, cg, &cells, &ok, &consistent)
 	/* one instantiation per two columns per lane from 4 on (round 6: steps of four left the mean job a sixth of its cells beyond its band's widest row) */
 	if(Cw <= 4)WTZ_EXTFR_CASE(4);
 	else if(Cw <= 6)WTZ_EXTFR_CASE(6);
@@ -367,13 +375,13 @@ WTZ_D bool wtz_extjob_run_fr(wtz_extjob_t *job, const wtz_params_t *Pm, wtz_pool
 	return true;
 }
 
-/* one wavefront per job */
-template<int TW>
+/* one wavefront per job; SP: the split-cost instantiation (I != D), chosen per launch from the context's setting (ext_split) */
+template<int TW, bool SP = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WTZ_OCC_EXTFR, 8))) wtz_kernel_extjobs_fr(wtz_extjob_t *jobs, const uint32_t *order, uint32_t n, const wtz_params_t *Pm, wtz_pool_t *pool, wtz_pool_t *tpool){
 	__shared__ uint64_t stb[TW];
 	const uint32_t b = blockIdx.x;
 	if(b >= n) return;
-	(void)wtz_extjob_run_fr<TW>(&jobs[order ? order[b] : b], Pm, pool, tpool, stb);
+	(void)wtz_extjob_run_fr<TW, SP>(&jobs[order ? order[b] : b], Pm, pool, tpool, stb);
 }
 
 #endif /* __HIPCC__ */

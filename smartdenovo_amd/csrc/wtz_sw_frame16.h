@@ -70,10 +70,12 @@ WTZ_D uint32_t wtz_even_bits(uint64_t x){
 
 /* one DP row.  hv / ev: H~ and E~ of the previous row in the previous frame on entry, of this row in this frame on exit; zw: the row's trace nibbles;
  * gm: maxima of h + column*E over groups of four registers; eqw: "bases equal" of run A in bits 0..C2-1, of run B in bits 16..16+C2-1;
- * bndp: the frame image of H(i-1, jb-1) in the HIGH half (what lane 0's run A reads through the lane shift); SFp: F~ at the band start in both halves */
-template<int C2, int S>
+ * bndp: the frame image of H(i-1, jb-1) in the HIGH half (what lane 0's run A reads through the lane shift); SFp: F~ at the band start in both halves.
+ * SP = false (I == D, the product): O / Op open both gap states.  SP = true (wtz_set_gap_open with I != D): Op = I in both halves opens the E state, Dp = D in both
+ * halves the F state - two packed adds per register instead of one - and O = D, the scalar the lane's F aggregate and carry-in take */
+template<int C2, int S, bool SP>
 WTZ_D void wtz_pk_row(uint32_t (&hv)[C2], uint32_t (&ev)[C2], uint32_t (&zw)[(C2 + 3) / 4], uint32_t (&gm)[(C2 + 3) / 4], const uint32_t eqw, const uint32_t bndp, const uint32_t SFp,
-		const int32_t SF, const int32_t O, const uint32_t MXp, const uint32_t Xpp, const uint32_t Op, const uint32_t (&ckp)[C2]){
+		const int32_t SF, const int32_t O, const uint32_t MXp, const uint32_t Xpp, const uint32_t Op, const uint32_t Dp, const uint32_t (&ckp)[C2]){
 	/* ---- pass 1: m~ into hv[] in place, the runs' F aggregates ---- */
 	uint32_t agg = 0x80008000u;
 	auto cell1 = [&](auto kc, const uint32_t src) -> uint32_t {
@@ -128,8 +130,9 @@ WTZ_D void wtz_pk_row(uint32_t (&hv)[C2], uint32_t (&ev)[C2], uint32_t (&zw)[(C2
 		const uint32_t t = wtz_pk_adds(m, Op);
 		const uint32_t s2 = wtz_pk_subs(t, e);                                     /* E extended */
 		const uint32_t en = wtz_pk_max(e, t);
-		const uint32_t s3 = wtz_pk_subs(t, f);                                     /* F extended */
-		f = wtz_pk_max(f, t);
+		const uint32_t tf = SP ? wtz_pk_adds(m, Dp) : t;                           /* kswx.h:174: the F state opens with D */
+		const uint32_t s3 = wtz_pk_subs(tf, f);                                    /* F extended */
+		f = wtz_pk_max(f, tf);
 		hv[k] = h; ev[k] = en;
 		/* the four signs into bits 15..12 of each half (two ops per merge: a shift and a v_bfi), then into the register's nibble of the row's trace word; bits
 		 * outside a nibble are never kept (the first register of a word brings garbage into the nibbles the next three overwrite; a last, incomplete word keeps it
@@ -150,7 +153,7 @@ WTZ_D void wtz_pk_row(uint32_t (&hv)[C2], uint32_t (&ev)[C2], uint32_t (&zw)[(C2
 
 /* traceback over the nibble trace of wtz_extend_shift_pk: wtz_shift_traceback<C, 64> with another staging step (dword q of lane l of a row holds the
  * registers 4q .. 4q+3 of the lane: run A's nibbles in bits 0..15, run B's in bits 16..31) */
-template<int C2>
+template<int C2, bool SP = false>
 WTZ_D bool wtz_shift_traceback_pk(wtz_aln_t &x, uint8_t **zchunk, const int32_t *zb, uint32_t zrow, uint32_t *lds, wtz_cigar_t &cigars, const wtz_tb_score *sc){
 	const int lane = (int)(threadIdx.x & 63);
 	constexpr int C = 2 * C2, CQ = (C2 + 3) / 4, NL = 64;
@@ -160,7 +163,7 @@ WTZ_D bool wtz_shift_traceback_pk(wtz_aln_t &x, uint8_t **zchunk, const int32_t 
 	uint32_t *S32 = lds; uint8_t *S8 = (uint8_t*)lds; uint8_t *Sd = S8 + 8192;
 	int32_t i_ = x.qe, j_ = x.te; uint32_t d_ = 0;
 	uint32_t run_op = 0xFFu, run_len = 0;
-	int32_t n_gap_runs = 0; bool consistent = true;
+	int32_t n_gap_runs = 0, n_del_runs = 0; bool consistent = true;
 	wtz_cigw_t Wr; Wr.v = &cigars; Wr.tail = 0;
 	int32_t cc = 0;
 	if(i_ >= 0) cc = j_ - wtz_as_global(zb)[i_];
@@ -227,7 +230,7 @@ WTZ_D bool wtz_shift_traceback_pk(wtz_aln_t &x, uint8_t **zchunk, const int32_t 
 				else if(d_ == 1){ i_--; x.ins++; cc += sft; }
 				else { j_--; x.del++; cc--; }
 				if(d_ == run_op) run_len++;
-				else { if(run_len) wtz_cigw_push(Wr, run_op, run_len); run_op = d_; run_len = 1; if(d_) n_gap_runs++; }
+				else { if(run_len) wtz_cigw_push(Wr, run_op, run_len); run_op = d_; run_len = 1; if(d_) n_gap_runs++; if constexpr(SP){ if(d_ == 2) n_del_runs++; } }
 			}
 		}
 		i_ = __builtin_amdgcn_readfirstlane(i_); j_ = __builtin_amdgcn_readfirstlane(j_); cc = __builtin_amdgcn_readfirstlane(cc);
@@ -236,22 +239,19 @@ WTZ_D bool wtz_shift_traceback_pk(wtz_aln_t &x, uint8_t **zchunk, const int32_t 
 	if(lane == 0){
 		if(run_len) wtz_cigw_push(Wr, run_op, run_len);
 		if(i_ >= 0){ x.ins += i_ + 1; wtz_cigw_push(Wr, 1, (uint32_t)(i_ + 1)); n_gap_runs++; }
-		if(j_ >= 0){ x.del += j_ + 1; wtz_cigw_push(Wr, 2, (uint32_t)(j_ + 1)); n_gap_runs++; }
+		if(j_ >= 0){ x.del += j_ + 1; wtz_cigw_push(Wr, 2, (uint32_t)(j_ + 1)); n_gap_runs++; n_del_runs++; }
 		wtz_cigw_finish(Wr);
 		wtz_cigar_reverse(cigars.a, cigars.n);
-		const int32_t nd = x.mat, MXd = sc->M - sc->X;
-		const long long S = (long long)x.score - sc->init - (long long)n_gap_runs * sc->O - (long long)sc->E * (x.ins + x.del) - (long long)sc->X * nd;
-		if(MXd == 0 || S % MXd != 0 || S / MXd < 0 || S / MXd > nd) consistent = false;
-		else { x.mat = (int32_t)(S / MXd); x.mis = nd - x.mat; }
+		consistent = wtz_tb_solve<SP>(x, sc, n_gap_runs, n_del_runs);
 		x.aln = x.mat + x.mis + x.ins + x.del; x.qe++; x.te++;
 	}
 	return __builtin_amdgcn_readfirstlane((int)consistent) != 0;
 }
 
 /* tp: LDS, 2*TWD dwords: the low-bit plane of the target in tp[0 .. TWD), the high-bit plane behind it */
-template<int C2, int TWD>
+template<int C2, int TWD, bool SP>
 WTZ_D wtz_aln_t wtz_extend_shift_pk(int32_t qlen, const wtz_seq_packed &query, int32_t tlen, const wtz_seq_packed &target, int32_t init_score,
-		int32_t ql, int32_t tl, int32_t W, int32_t M, int32_t X, int32_t O, int32_t E, int32_t T, int32_t bias, int32_t NG, int32_t SH,
+		int32_t ql, int32_t tl, int32_t W, int32_t M, int32_t X, int32_t O, int32_t Dc, int32_t E, int32_t T, int32_t bias, int32_t NG, int32_t SH,
 		uint32_t *tp, wtz_trace_t &tr, wtz_pool_t *pool, wtz_cigar_t &cigars, unsigned long long *cells, bool *ok, bool *consistent){
 	const int lane = (int)(threadIdx.x & 63);
 	constexpr int C = 2 * C2, CQ = (C2 + 3) / 4;
@@ -263,6 +263,9 @@ WTZ_D wtz_aln_t wtz_extend_shift_pk(int32_t qlen, const wtz_seq_packed &query, i
 	ql = __builtin_amdgcn_readfirstlane(ql); tl = __builtin_amdgcn_readfirstlane(tl); W = __builtin_amdgcn_readfirstlane(W); bias = __builtin_amdgcn_readfirstlane(bias);
 	NG = __builtin_amdgcn_readfirstlane(NG); SH = __builtin_amdgcn_readfirstlane(SH);
 	M = __builtin_amdgcn_readfirstlane(M); X = __builtin_amdgcn_readfirstlane(X); O = __builtin_amdgcn_readfirstlane(O); E = __builtin_amdgcn_readfirstlane(E); T = __builtin_amdgcn_readfirstlane(T);
+	/* O = I, the cost of the E state and of column -1; D = the cost of the F state and of row -1 (SP = false: the same value, the same register) */
+	int32_t D = O;
+	if constexpr(SP) D = __builtin_amdgcn_readfirstlane(Dc);
 	const uint32_t zrow = (uint32_t)CQ * 256u;
 	if(!wtz_trace_prepare(tr, pool, zrow, ql, true)){ *ok = false; return x; }
 	uint8_t **zchunk = tr.chunk; int32_t *zb = tr.zb;
@@ -275,6 +278,8 @@ WTZ_D wtz_aln_t wtz_extend_shift_pk(int32_t qlen, const wtz_seq_packed &query, i
 	const int32_t colrel0 = lane * C;
 	const int32_t MX = M - X, Xp = X - 2 * E;
 	const uint32_t MXp = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)wtz_pk2(MX, MX)), Xpp = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)wtz_pk2(Xp, Xp)), Op = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)wtz_pk2(O, O));
+	uint32_t Dp = Op;
+	if constexpr(SP) Dp = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)wtz_pk2(D, D));
 	/* column term of the arg-max value of register k: k*E (run A), (C2 + k)*E (run B); wave-uniform */
 	uint32_t ckp[C2];
 	#pragma unroll
@@ -288,7 +293,7 @@ WTZ_D wtz_aln_t wtz_extend_shift_pk(int32_t qlen, const wtz_seq_packed &query, i
 		#pragma unroll
 		for(int hh = 0; hh < 2; hh++){
 			const int32_t c = colrel0 + hh * C2 + p - 1;
-			const int32_t hr = (c < 0) ? init_score : init_score + O + E * (c + 1);
+			const int32_t hr = (c < 0) ? init_score : init_score + D + E * (c + 1);
 			vh[hh] = hr - (c - 1) * E - bias;     /* G(-1,c) */
 			ve[hh] = NG - c * E - bias;           /* E~(0,c) */
 		}
@@ -344,9 +349,9 @@ WTZ_D wtz_aln_t wtz_extend_shift_pk(int32_t qlen, const wtz_seq_packed &query, i
 		const int32_t SF = NG - (i + jb) * E - bias;
 		const uint32_t bndp = (uint32_t)bnd << 16, SFp = wtz_pk2(SF, SF);
 		uint32_t zw[CQ], gm[CQ];
-		if(s == 1)      wtz_pk_row<C2, 1>(hv, ev, zw, gm, eqw, bndp, SFp, SF, O, MXp, Xpp, Op, ckp);
-		else if(s == 0) wtz_pk_row<C2, 0>(hv, ev, zw, gm, eqw, bndp, SFp, SF, O, MXp, Xpp, Op, ckp);
-		else            wtz_pk_row<C2, 2>(hv, ev, zw, gm, eqw, bndp, SFp, SF, O, MXp, Xpp, Op, ckp);
+		if(s == 1)      wtz_pk_row<C2, 1, SP>(hv, ev, zw, gm, eqw, bndp, SFp, SF, D, MXp, Xpp, Op, Dp, ckp);
+		else if(s == 0) wtz_pk_row<C2, 0, SP>(hv, ev, zw, gm, eqw, bndp, SFp, SF, D, MXp, Xpp, Op, Dp, ckp);
+		else            wtz_pk_row<C2, 2, SP>(hv, ev, zw, gm, eqw, bndp, SFp, SF, D, MXp, Xpp, Op, Dp, ckp);
 		const int32_t nvt = je - jb;                       /* band-relative column of the first cell beyond the band end */
 		/* ---- row maximum over the cells inside the band and its FIRST arg-max (kswx.h:172) ---- */
 		const int32_t vcut = __builtin_amdgcn_readfirstlane(nvt / C2), kcut = __builtin_amdgcn_readfirstlane(nvt % C2);      /* the run the band end cuts through, its first cell beyond */
@@ -485,8 +490,8 @@ WTZ_D wtz_aln_t wtz_extend_shift_pk(int32_t qlen, const wtz_seq_packed &query, i
 	if(gmax > 0 && gmax >= mx + T){ x.score = gmax; x.qe = gi; x.te = gj; }
 	else { x.score = mx; x.qe = mi; x.te = mj; }
 	__threadfence_block();
-	const wtz_tb_score sc = { M, X, O, E, init_score };
-	if(!wtz_shift_traceback_pk<C2>(x, zchunk, zb, zrow, tp, cigars, &sc)) *ok = false, *consistent = false;
+	const wtz_tb_score sc = { M, X, O, D, E, init_score };
+	if(!wtz_shift_traceback_pk<C2, SP>(x, zchunk, zb, zrow, tp, cigars, &sc)) *ok = false, *consistent = false;
 	if(__builtin_amdgcn_readfirstlane((int)lost)) *ok = false, *consistent = false;      /* the arg-max search came back empty: never observed; the job stays open for the 32-bit form */
 	return wtz_bcast_aln(x);
 }
@@ -507,8 +512,12 @@ WTZ_D wtz_aln_t wtz_extend_shift_pk(int32_t qlen, const wtz_seq_packed &query, i
  *     like the reference's.  The decisions on the path of the result, the row maxima and their arg-max columns compare real values with each other or a real
  *     winner with a family loser: they are the reference's.  The two places that test a value against zero (row maximum, target-end cell) take a family value
  *     (<= *sh = NG + M*min(ql,tl)) for what it is in the reference: negative. */
+/* O in both window functions: the opening cost of the larger magnitude, min(I, D) (wtz_set_gap_open; I == D == params.O without it) - every bound below that
+ * names O is a bound on what ONE opening can take from a value, whichever state it opens.
+ * SP = false: the caller knows I == D (the single-cost instantiation) and I is read alone. */
+template<bool SP = true>
 WTZ_D bool wtz_pk_window(const wtz_params_t *Pm, int32_t init_score, int32_t ql, int32_t tl, int32_t *bias, int32_t *ng, int32_t *sh){
-	const long long M = Pm->M, X = Pm->X, O = Pm->O, E = Pm->E;
+	const long long M = Pm->M, X = Pm->X, O = (SP && Pm->D < Pm->I) ? Pm->D : Pm->I, E = Pm->E;
 	if(E > 0 || E < -255 || X > 0 || M < 0 || O > 0 || M == X || M - X > 4096) return false;
 	const long long aE = -E, aO = -O, aX = -X, Xp = X - 2 * E, Xm = Xp < 0 ? Xp : 0;
 	const long long mn = ql < tl ? ql : tl;
@@ -534,7 +543,7 @@ WTZ_D bool wtz_pk_window(const wtz_params_t *Pm, int32_t init_score, int32_t ql,
  * when a stage's items are dealt to the two forms all of it is known but the left extension's own gain: a range.)  Window (a) holds up to an init_score Ia,
  * window (b) from Ib on. */
 WTZ_D bool wtz_pk_window_range(const wtz_params_t *Pm, int32_t ql, int32_t tl, long long i_lo, long long i_hi){
-	const long long M = Pm->M, X = Pm->X, O = Pm->O, E = Pm->E;
+	const long long M = Pm->M, X = Pm->X, O = Pm->I < Pm->D ? Pm->I : Pm->D, E = Pm->E;
 	if(E > 0 || E < -255 || X > 0 || M < 0 || O > 0 || M == X || M - X > 4096) return false;
 	if(i_lo < 0) i_lo = 0;
 	if(i_hi < 0) i_hi = 0;
@@ -555,24 +564,25 @@ WTZ_D bool wtz_pk_window_range(const wtz_params_t *Pm, int32_t ql, int32_t tl, l
 
 /* one K-sw3 job on the calling wavefront in the packed form; false = declined (outside the window or the envelope of wtz_extjob_run_fr: the job stays open).
  * stb: TW 64-bit words of LDS of this wave. */
-template<int TW>
+template<int TW, bool SP>
 WTZ_D bool wtz_extjob_run_pk(wtz_extjob_t *job, const wtz_params_t *Pm, wtz_pool_t *pool, wtz_pool_t *tpool, uint64_t *stb){
 	if(!job->valid || job->done) return true;
 	const int lane = (int)(threadIdx.x & 63);
 	if(job->qlen <= 0 || job->tlen <= 0) return false;
 	const int32_t init_score = job->init_score < 0 ? 0 : job->init_score;
 	int32_t W = job->W, ql, tl, n_col;
-	wtz_ext_geometry(job->qlen, job->tlen, init_score, W, Pm->M, Pm->O, Pm->O, Pm->E, Pm->T, ql, tl, n_col);
+	const int32_t pI = Pm->I, pD = SP ? Pm->D : pI;
+	wtz_ext_geometry(job->qlen, job->tlen, init_score, W, Pm->M, pI, pD, Pm->E, Pm->T, ql, tl, n_col);
 	const int32_t Cw = (n_col + 63) / 64;
 	if(Cw > 32 || (tl + 31) / 32 + 3 > TW || (ql + 63) / 64 > WTZ_TRACE_MAXCHUNK) return false;
 	int32_t bias = 0, ng = -10000, sh = 0;
-	if(!wtz_pk_window(Pm, init_score, ql, tl, &bias, &ng, &sh)) return false;
+	if(!wtz_pk_window<SP>(Pm, init_score, ql, tl, &bias, &ng, &sh)) return false;
 	wtz_trace_t tr; tr.chunk = NULL; tr.zb = NULL; tr.n_chunk = 0; tr.zrow = 0; tr.cap_rows = 0;
 	wtz_cigar_t cg; cg.a = NULL; cg.n = cg.cap = 0; cg.pool = pool; cg.bad = 0;
 	if(lane == 0) cg.init(pool, (uint32_t)ql / 2u + 16u);
 	unsigned long long cells = 0; bool ok = true, consistent = true;
 	wtz_aln_t x;
-#define WTZ_EXTPK_CASE(CM) x = wtz_extend_shift_pk<CM, TW>(job->qlen, job->q, job->tlen, job->t, job->init_score, ql, tl, W, Pm->M, Pm->X, Pm->O, Pm->E, Pm->T, bias, ng, sh, (uint32_t*)stb, tr, tpool, cg, &cells, &ok, &consistent)
+#define WTZ_EXTPK_CASE(CM) x = wtz_extend_shift_pk<CM, TW, SP>(job->qlen, job->q, job->tlen, job->t, job->init_score, ql, tl, W, Pm->M, Pm->X, pI, pD, Pm->E, Pm->T, bias, ng, sh, (uint32_t*)stb, tr, tpool, cg, &cells, &ok, &consistent)
 	/* one instantiation per register of a lane (two columns): a job's band is at most two columns per lane narrower than its class */
 	if(Cw <= 4) WTZ_EXTPK_CASE(2);
 	else if(Cw <= 6) WTZ_EXTPK_CASE(3);
@@ -595,13 +605,13 @@ WTZ_D bool wtz_extjob_run_pk(wtz_extjob_t *job, const wtz_params_t *Pm, wtz_pool
 	return true;
 }
 
-/* one wavefront per job */
-template<int TW>
+/* one wavefront per job; SP: the split-cost instantiation (wtz_sw_frame.h) */
+template<int TW, bool SP = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WTZ_OCC_EXTPK, 8))) wtz_kernel_extjobs_pk(wtz_extjob_t *jobs, const uint32_t *order, uint32_t n, const wtz_params_t *Pm, wtz_pool_t *pool, wtz_pool_t *tpool){
 	__shared__ uint64_t stb[TW];
 	const uint32_t b = blockIdx.x;
 	if(b >= n) return;
-	(void)wtz_extjob_run_pk<TW>(&jobs[order ? order[b] : b], Pm, pool, tpool, stb);
+	(void)wtz_extjob_run_pk<TW, SP>(&jobs[order ? order[b] : b], Pm, pool, tpool, stb);
 }
 
 #endif /* __HIPCC__ */

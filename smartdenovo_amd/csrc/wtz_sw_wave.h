@@ -510,10 +510,25 @@ WTZ_D void wtz_cigw_finish(wtz_cigw_t &w){ if(w.tail){ w.v->push(w.tail); w.tail
  * went with that kernel); the walk counts diagonal steps and gap runs, and matches / mismatches follow from the score: every gap run of the path was opened once (a run ends in the diagonal step
  * of the cell it was opened from - kswx.h:175-183 opens from m, not from H - so two runs never touch), hence
  *     score - init = M*mat + X*mis + runs*O + E*(ins + del),   mat + mis = diagonal steps.
- * `sc` = {M, X, O, E, init_score (clamped)}; returns false when the identity does not come out in integers (never observed; the caller then leaves the job to the general kernel).
+ * With two opening costs (SP = true, wtz_set_gap_open with I != D) the argument is the same - every run, the two tails of the walk included, was opened once from m:
+ * a run of query-only steps (op 1; the leftover rows at the end of the walk are one, kswx.h:220-223, opened by column -1: kswx.h:152) with I, a run of target-only
+ * steps (op 2; the leftover columns, kswx.h:224-227, opened by row -1: kswx.h:143) with D - so the walk counts the two kinds apart and solves
+ *     score - init = M*mat + X*mis + I*runs_ins + D*runs_del + E*(ins + del).
+ * `sc` = {M, X, I, D, E, init_score (clamped)} (SP = false reads I for both); returns false when the identity does not come out in integers (never observed; the caller then leaves the job to the general kernel).
  * wtz_shift_traceback_pk (wtz_sw_frame16.h) is this function with the nibble trace's staging step. ---- */
-struct wtz_tb_score { int32_t M, X, O, E, init; };
-template<int C, int NL>
+struct wtz_tb_score { int32_t M, X, I, D, E, init; };
+/* the identity above solved for mat: false = it does not come out in integers */
+template<bool SP>
+WTZ_D bool wtz_tb_solve(wtz_aln_t &x, const wtz_tb_score *sc, int32_t n_gap_runs, int32_t n_del_runs){
+	/* n_gap_runs: all runs; n_del_runs: those of op 2 (counted with SP = true only) */
+	const int32_t nd = x.mat, MXd = sc->M - sc->X;
+	long long S = (long long)x.score - sc->init - (long long)n_gap_runs * sc->I - (long long)sc->E * (x.ins + x.del) - (long long)sc->X * nd;
+	if constexpr(SP) S -= (long long)n_del_runs * ((long long)sc->D - sc->I);
+	if(MXd == 0 || S % MXd != 0 || S / MXd < 0 || S / MXd > nd) return false;
+	x.mat = (int32_t)(S / MXd); x.mis = nd - x.mat;
+	return true;
+}
+template<int C, int NL, bool SP = false>
 WTZ_D bool wtz_shift_traceback(wtz_aln_t &x, uint8_t **zchunk, const int32_t *zb, uint32_t zrow, uint64_t *tb, wtz_cigar_t &cigars, const wtz_tb_score *sc){
 	const int lane = (int)(threadIdx.x & 63);
 	constexpr int C4 = (C + 3) / 4;
@@ -523,7 +538,7 @@ WTZ_D bool wtz_shift_traceback(wtz_aln_t &x, uint8_t **zchunk, const int32_t *zb
 	uint32_t *S32 = (uint32_t*)tb; uint8_t *S8 = (uint8_t*)tb; uint8_t *Sd = S8 + 8192;
 	int32_t i_ = x.qe, j_ = x.te; uint32_t d_ = 0;
 	uint32_t run_op = 0xFFu, run_len = 0;
-	int32_t n_gap_runs = 0; bool consistent = true;
+	int32_t n_gap_runs = 0, n_del_runs = 0; bool consistent = true;
 	wtz_cigw_t Wr; Wr.v = &cigars; Wr.tail = 0;
 	int32_t cc = 0;
 	if(i_ >= 0) cc = j_ - wtz_as_global(zb)[i_];
@@ -586,7 +601,7 @@ WTZ_D bool wtz_shift_traceback(wtz_aln_t &x, uint8_t **zchunk, const int32_t *zb
 				else if(d_ == 1){ i_--; x.ins++; cc += sft; }
 				else { j_--; x.del++; cc--; }
 				if(d_ == run_op) run_len++;
-				else { if(run_len) wtz_cigw_push(Wr, run_op, run_len); run_op = d_; run_len = 1; if(d_) n_gap_runs++; }
+				else { if(run_len) wtz_cigw_push(Wr, run_op, run_len); run_op = d_; run_len = 1; if(d_) n_gap_runs++; if constexpr(SP){ if(d_ == 2) n_del_runs++; } }
 			}
 		}
 		i_ = __builtin_amdgcn_readfirstlane(i_); j_ = __builtin_amdgcn_readfirstlane(j_); cc = __builtin_amdgcn_readfirstlane(cc);
@@ -595,13 +610,10 @@ WTZ_D bool wtz_shift_traceback(wtz_aln_t &x, uint8_t **zchunk, const int32_t *zb
 	if(lane == 0){
 		if(run_len) wtz_cigw_push(Wr, run_op, run_len);
 		if(i_ >= 0){ x.ins += i_ + 1; wtz_cigw_push(Wr, 1, (uint32_t)(i_ + 1)); n_gap_runs++; }
-		if(j_ >= 0){ x.del += j_ + 1; wtz_cigw_push(Wr, 2, (uint32_t)(j_ + 1)); n_gap_runs++; }
+		if(j_ >= 0){ x.del += j_ + 1; wtz_cigw_push(Wr, 2, (uint32_t)(j_ + 1)); n_gap_runs++; n_del_runs++; }
 		wtz_cigw_finish(Wr);
 		wtz_cigar_reverse(cigars.a, cigars.n);
-		const int32_t nd = x.mat, MXd = sc->M - sc->X;
-		const long long S = (long long)x.score - sc->init - (long long)n_gap_runs * sc->O - (long long)sc->E * (x.ins + x.del) - (long long)sc->X * nd;
-		if(MXd == 0 || S % MXd != 0 || S / MXd < 0 || S / MXd > nd) consistent = false;
-		else { x.mat = (int32_t)(S / MXd); x.mis = nd - x.mat; }
+		consistent = wtz_tb_solve<SP>(x, sc, n_gap_runs, n_del_runs);
 		x.aln = x.mat + x.mis + x.ins + x.del; x.qe++; x.te++;
 	}
 	return __builtin_amdgcn_readfirstlane((int)consistent) != 0;
@@ -631,22 +643,22 @@ __global__ void __launch_bounds__(64) wtz_kernel_extjobs(wtz_extjob_t *jobs, con
 	}
 	wtz_wave_lds_t L; L.Hs = sHs; L.Es = sEs; L.tb = stb; L.PM = P - 1; L.tw = TW;
 	int32_t W = job->W, ql, tl, n_col;
-	wtz_ext_geometry(job->qlen, job->tlen, init_score, W, Pm->M, Pm->O, Pm->O, Pm->E, Pm->T, ql, tl, n_col);
+	wtz_ext_geometry(job->qlen, job->tlen, init_score, W, Pm->M, Pm->I, Pm->D, Pm->E, Pm->T, ql, tl, n_col);
 	if(wtz_wave_fits(L, n_col, tl, ql)){
 		wtz_trace_t tr; tr.chunk = NULL; tr.zb = NULL; tr.n_chunk = 0; tr.zrow = 0; tr.cap_rows = 0;
 		wtz_cigar_t cg; if(lane == 0) cg.init(pool, 64);
 		unsigned long long cells = 0; bool ok = true;
 		const int32_t Cw = (((n_col + 63) / 64) | 1);
 		wtz_aln_t x;
-		if(Cw <= 8)       x = wtz_extend_shift_wave_rt<8>(job->qlen, job->q, job->tlen, job->t, job->init_score, job->W, Pm->M, Pm->X, Pm->O, Pm->O, Pm->E, Pm->T, L, tr, tpool, cg, &cells, &ok);
-		else if(Cw <= 16) x = wtz_extend_shift_wave_rt<16>(job->qlen, job->q, job->tlen, job->t, job->init_score, job->W, Pm->M, Pm->X, Pm->O, Pm->O, Pm->E, Pm->T, L, tr, tpool, cg, &cells, &ok);
-		else              x = wtz_extend_shift_wave_rt<32>(job->qlen, job->q, job->tlen, job->t, job->init_score, job->W, Pm->M, Pm->X, Pm->O, Pm->O, Pm->E, Pm->T, L, tr, tpool, cg, &cells, &ok);
+		if(Cw <= 8)       x = wtz_extend_shift_wave_rt<8>(job->qlen, job->q, job->tlen, job->t, job->init_score, job->W, Pm->M, Pm->X, Pm->I, Pm->D, Pm->E, Pm->T, L, tr, tpool, cg, &cells, &ok);
+		else if(Cw <= 16) x = wtz_extend_shift_wave_rt<16>(job->qlen, job->q, job->tlen, job->t, job->init_score, job->W, Pm->M, Pm->X, Pm->I, Pm->D, Pm->E, Pm->T, L, tr, tpool, cg, &cells, &ok);
+		else              x = wtz_extend_shift_wave_rt<32>(job->qlen, job->q, job->tlen, job->t, job->init_score, job->W, Pm->M, Pm->X, Pm->I, Pm->D, Pm->E, Pm->T, L, tr, tpool, cg, &cells, &ok);
 		if(lane == 0){ job->x = x; job->cigar = cg.a; job->cigar_len = cg.n; job->bad = (!ok || cg.bad); job->cells = cells; job->done = 3; }
 	} else if(lane == 0){
 		wtz_swmem_t mem; wtz_swmem_init(mem, tpool);
 		wtz_cigar_t cg; cg.init(pool, 64);
 		unsigned long long cells = 0;
-		wtz_aln_t x = wtz_extend_shift(job->qlen, job->q, job->tlen, job->t, job->init_score, job->W, Pm->M, Pm->X, Pm->O, Pm->O, Pm->E, Pm->T, mem, cg, &cells);
+		wtz_aln_t x = wtz_extend_shift(job->qlen, job->q, job->tlen, job->t, job->init_score, job->W, Pm->M, Pm->X, Pm->I, Pm->D, Pm->E, Pm->T, mem, cg, &cells);
 		job->x = x; job->cigar = cg.a; job->cigar_len = cg.n; job->bad = (mem.bad || cg.bad); job->cells = cells; job->done = 3;
 	}
 }
@@ -912,7 +924,7 @@ template<bool FULL, bool TEST>
 WTZ_D void wtz_fixed_problem_wave(int32_t qlen, const wtz_seq_packed &q, int32_t tlen, const wtz_seq_packed &t, int32_t score_in, const wtz_params_t *P,
 		const wtz_wave_lds_t &L, uint8_t *ztr, int32_t ztr_bytes, wtz_cigar_t &tmp, wtz_swmem_t &mem, wtz_pool_t *pool, unsigned long long *cells, int force, wtz_fixres_t &R){
 	const int lane = (int)(threadIdx.x & 63);
-	const int32_t M = P->M, X = P->X, I = P->O, D = P->O, E = P->E, T = P->T;
+	const int32_t M = P->M, X = P->X, I = P->I, D = P->D, E = P->E, T = P->T;
 	wtz_aln_t y; memset(&y, 0, sizeof y);
 	R.runs = NULL; R.n_runs = 0; R.lds_runs = false; R.ok = true; R.defer = false; R.form = 0;
 	const unsigned long long pt0 = WTZ_PROF_T(); (void)pt0;
@@ -984,7 +996,7 @@ template<bool FULL = true>
 WTZ_D wtz_aln_t wtz_align_window_wave(const wtz_readview &pb1, const wtz_readview &pb2, const wtz_win_t &win, const wtz_zhit_t *anchors,
 		wtz_cigar_t &cigar, wtz_cigar_t &tmp, const wtz_params_t *P, wtz_pool_t *pool, int32_t *lds, unsigned long long *cells, bool *ok, bool *defer = NULL){
 	const int lane = (int)(threadIdx.x & 63);
-	const int32_t M = P->M, I = P->O, D = P->O, E = P->E;
+	const int32_t M = P->M, I = P->I, D = P->D, E = P->E;
 	/* LDS slice: 128 target words (1 KB), then the 4-bit trace of the register DP with its run list at the top end (7 KB) */
 	wtz_wave_lds_t L; L.tb = (uint64_t*)lds; L.Hs = lds + 256; L.Es = lds + 768; L.PM = 511; L.tw = 128; L.qw = (uint32_t*)(lds + WTZ_WINALIGN_LDS_BYTES / 4);
 	uint8_t *ztr = (uint8_t*)(lds + 256); const int32_t ztr_bytes = WTZ_WINALIGN_LDS_BYTES - 1024;

@@ -409,7 +409,7 @@ WTZ_HD void wtz_task_lplan(uint32_t t, const wtz_env_t &V, const wtz_wintask_t *
 	const wtz_win_t &w = it.win[tasks[t].widx];
 	const wtz_readview pb1 = wtz_view(V.R, it.q, 0), pb2 = wtz_view(V.R, it.c, it.dir);
 	const uint32_t base = woff[t], na = w.anchors[1] - w.anchors[0];
-	const int32_t M = P->M, I = P->O, D = P->O, E = P->E, T = P->T;
+	const int32_t M = P->M, I = P->I, D = P->D, E = P->E, T = P->T;
 	int32_t te = 0, qe = 0; bool first = true, fb = false, ended = false;
 	uint32_t cc[4] = {0u, 0u, 0u, 0u}, n_used = 0;
 	for(uint32_t k0 = 0; k0 < na; k0 += 4){
@@ -481,7 +481,8 @@ WTZ_HD void wtz_task_lplan(uint32_t t, const wtz_env_t &V, const wtz_wintask_t *
 
 /* one wavefront = WTZ_NLANES problems of the shape-sorted order[lo, hi): relative-mode K-sw1, forward part; the wave's trace rows stay in the
  * transient pool (wtr[gw] = their base, wrm[gw] = rows per lane) for the traceback kernel */
-template<int NC>
+/* SP = false: the launch knows the context's two gap-open costs are equal (the default, wtz_set_gap_open never called): D is I, one value, as before the costs were two */
+template<int NC, bool SP = true>
 WTZ_HD void wtz_task_ldp(uint32_t gw, uint32_t wv, const wtz_env_t &V, const wtz_wintask_t *tasks, const wtz_alnitem_t *items, const uint32_t *order, uint32_t lo, uint32_t hi,
 		const wtz_lprob_t *prob, wtz_lres_t *res, uint64_t *wtr, uint32_t *wrm){
 	const wtz_params_t *P = V.P;
@@ -490,7 +491,7 @@ WTZ_HD void wtz_task_ldp(uint32_t gw, uint32_t wv, const wtz_env_t &V, const wtz
 	const uint32_t slot = live ? order[idx] : 0u;
 	wtz_lprob_t pr; pr.win = 0; pr.qoff = pr.toff = 0; pr.qlen = pr.tlen = 0; pr.run_off = 0;
 	if(live) pr = prob[slot];
-	const int32_t M = P->M, X = P->X, I = P->O, D = P->O, E = P->E, T = P->T;
+	const int32_t M = P->M, X = P->X, I = P->I, D = SP ? P->D : I, E = P->E, T = P->T;
 	int32_t W = P->w, ql = 0, tl = 0, n_col = 0;
 	wtz_seq_packed q, tt; q.bits = tt.bits = V.R.bits; q.start = tt.start = 0; q.strand = tt.strand = 1; q.comp = tt.comp = 0;
 	if(live){
@@ -523,7 +524,7 @@ WTZ_HD void wtz_task_ltb(uint32_t gw, uint32_t wv, uint32_t RS, const wtz_env_t 
 	const wtz_lprob_t pr = prob[slot];
 	wtz_lres_t R = res[slot];
 	int32_t W = P->w, ql, tl, n_col;
-	wtz_ext_geometry(pr.qlen, pr.tlen, 0, W, P->M, P->O, P->O, P->E, P->T, ql, tl, n_col);
+	wtz_ext_geometry(pr.qlen, pr.tlen, 0, W, P->M, P->I, P->D, P->E, P->T, ql, tl, n_col);
 	const wtz_alnitem_t &it = items[tasks[pr.win].item];
 	const wtz_seq_packed q = wtz_view(V.R, it.c, it.dir).sub(pr.qoff, 1), tt = wtz_view(V.R, it.q, 0).sub(pr.toff, 1);
 	const uint32_t *tr = (const uint32_t*)(uintptr_t)pa;      /* lane-interleaved, as the DP kernel wrote it */
@@ -533,14 +534,15 @@ WTZ_HD void wtz_task_ltb(uint32_t gw, uint32_t wv, uint32_t RS, const wtz_env_t 
 
 /* the four shape classes in ONE launch (widest band first = longest tasks first): wave wv -> class by the launch's wave ranges */
 typedef struct { uint32_t wend[4], lo[4], hi[4]; } wtz_lclass_t;      /* index 0..3 = band classes 104 / 64 / 32 / 16 */
+template<bool SP = true>
 WTZ_HD void wtz_task_ldp_all(uint32_t wv, const wtz_lclass_t &L, const wtz_env_t &V, const wtz_wintask_t *tasks, const wtz_alnitem_t *items, const uint32_t *order,
 		const wtz_lprob_t *prob, wtz_lres_t *res, uint64_t *wtr, uint32_t *wrm){
 	uint32_t k = 0; while(k < 3 && wv >= L.wend[k]) k++;
 	const uint32_t wl = wv - (k ? L.wend[k - 1] : 0u);
-	if(k == 0)      wtz_task_ldp<104>(wv, wl, V, tasks, items, order, L.lo[0], L.hi[0], prob, res, wtr, wrm);
-	else if(k == 1) wtz_task_ldp<64>(wv, wl, V, tasks, items, order, L.lo[1], L.hi[1], prob, res, wtr, wrm);
-	else if(k == 2) wtz_task_ldp<32>(wv, wl, V, tasks, items, order, L.lo[2], L.hi[2], prob, res, wtr, wrm);
-	else            wtz_task_ldp<16>(wv, wl, V, tasks, items, order, L.lo[3], L.hi[3], prob, res, wtr, wrm);
+	if(k == 0)      wtz_task_ldp<104, SP>(wv, wl, V, tasks, items, order, L.lo[0], L.hi[0], prob, res, wtr, wrm);
+	else if(k == 1) wtz_task_ldp<64, SP>(wv, wl, V, tasks, items, order, L.lo[1], L.hi[1], prob, res, wtr, wrm);
+	else if(k == 2) wtz_task_ldp<32, SP>(wv, wl, V, tasks, items, order, L.lo[2], L.hi[2], prob, res, wtr, wrm);
+	else            wtz_task_ldp<16, SP>(wv, wl, V, tasks, items, order, L.lo[3], L.hi[3], prob, res, wtr, wrm);
 }
 WTZ_HD void wtz_task_ltb_all(uint32_t wv, const wtz_lclass_t &L, const wtz_env_t &V, const wtz_wintask_t *tasks, const wtz_alnitem_t *items, const uint32_t *order,
 		const wtz_lprob_t *prob, const uint32_t *runoff, uint32_t *runs, wtz_lres_t *res, const uint64_t *wtr, const uint32_t *wrm){
@@ -607,7 +609,7 @@ WTZ_HD void wtz_task_lfold(uint32_t t, const wtz_env_t &V, const wtz_wintask_t *
 	const wtz_win_t &w = it.win[tasks[t].widx];
 	const wtz_readview pb1 = wtz_view(V.R, it.q, 0), pb2 = wtz_view(V.R, it.c, it.dir);
 	const uint32_t base = woff[t], na = w.anchors[1] - w.anchors[0];
-	const int32_t M = P->M, I = P->O, D = P->O, E = P->E;
+	const int32_t M = P->M, I = P->I, D = P->D, E = P->E;
 	wtz_reg_t reg; memset(&reg, 0, sizeof reg);
 	wtz_lcig_t cw; cw.v.init(V.pool, na * 14u + 16u); cw.tail = 0;
 	wtz_aln_t x; memset(&x, 0, sizeof x);
@@ -700,10 +702,10 @@ typedef struct { int32_t score; bool from_reg, want_defer; int32_t bad; uint32_t
  *      1 / 2 / 4 / 8 band columns per lane (4-bit trace in the LDS slice or in the pool), the LDS-ring wave DP (narrow slice, or the
  *      72 KB slice of the wide launch), the scalar body - and runs it.  TEST = true (wtz_test_dp, function-level parity vectors): `force`
  *      names the form (C | 16 = trace in the pool, 32 = LDS-ring wave DP, 255 = scalar body); R.form = -1 = outside that form's envelope. ---- */
-template<bool TEST>
+template<bool TEST, bool SP = true>
 WTZ_D void wtz_gap_problem_wave(int32_t dq, const wtz_seq_packed &q, int32_t dt, const wtz_seq_packed &tt, const wtz_params_t *P, int32_t w,
 		int32_t *lds, uint32_t wide_lds, bool may_defer, wtz_pool_t *pool, wtz_cigar_t &tmp, wtz_trace_t &tr, wtz_swmem_t &mem, int force, wtz_gapdp_t &R){
-	const int32_t M = P->M, X = P->X, I = P->O, D = P->O, E = P->E;
+	const int32_t M = P->M, X = P->X, I = P->I, D = SP ? P->D : I, E = P->E;
 	/* LDS slice: 128 sequence words (1 KB), then either the H/E rings of the general wave DP or the 4-bit trace of the
 	 * register DP with its run list at the top end */
 	wtz_wave_lds_t L; L.tb = (uint64_t*)lds; L.Hs = lds + 256; L.Es = lds + 768; L.PM = 511; L.tw = 128;
@@ -788,6 +790,7 @@ WTZ_D void wtz_gap_problem_wave(int32_t dq, const wtz_seq_packed &q, int32_t dt,
 }
 #endif
 
+template<bool SP = true>
 WTZ_HD void wtz_task_gap(uint32_t t, const wtz_env_t &V, const wtz_wintask_t *tasks, const wtz_alnitem_t *items, wtz_gapres_t *gaps,
 		uint32_t *defer = NULL, const uint32_t *list = NULL, uint32_t wide_lds = 0){
 	if(list) t = list[1 + t];
@@ -801,7 +804,7 @@ WTZ_HD void wtz_task_gap(uint32_t t, const wtz_env_t &V, const wtz_wintask_t *ta
 	int32_t prev = -1;
 	for(int32_t j = (int32_t)k - 1; j >= 0; j--) if(it.regs[j].pass == 1){ prev = j; break; }
 	if(prev < 0){ if(WTZ_LANE == 0) *slot = g; return; }
-	const int32_t M = P->M, X = P->X, I = P->O, D = P->O, E = P->E;
+	const int32_t M = P->M, X = P->X, I = P->I, D = SP ? P->D : I, E = P->E;
 	const wtz_reg_t *reg1 = &it.regs[prev], *reg2 = &it.regs[k];
 	const wtz_readview pb1 = wtz_view(V.R, it.q, 0), pb2 = wtz_view(V.R, it.c, it.dir);
 	const int32_t dq = reg2->x.qb - reg1->x.qe, dt = reg2->x.tb - reg1->x.te;
@@ -818,7 +821,7 @@ WTZ_HD void wtz_task_gap(uint32_t t, const wtz_env_t &V, const wtz_wintask_t *ta
 		for(;;){
 			if(w < WTZ_ABSDIFF(dq, dt)){ w <<= 1; continue; }
 			wtz_gapdp_t G;
-			wtz_gap_problem_wave<false>(dq, q, dt, tt, P, w, lds, wide_lds, defer != NULL, V.pool, tmp, tr, mem, 0, G);
+			wtz_gap_problem_wave<false, SP>(dq, q, dt, tt, P, w, lds, wide_lds, defer != NULL, V.pool, tmp, tr, mem, 0, G);
 			if(G.want_defer){
 				if(WTZ_LANE == 0){ const uint32_t idx = atomicAdd(&defer[0], 1u); defer[1 + idx] = t; }
 				return;
@@ -916,7 +919,7 @@ WTZ_HD void wtz_task_gplan(uint32_t t, const wtz_env_t &V, const wtz_wintask_t *
 #endif
 	gp[t] = G; runcap[t] = cap; key[t] = ky; val[t] = t; done[t] = dn;
 }
-template<int NC>
+template<int NC, bool SP = true>
 WTZ_HD void wtz_task_gdp(uint32_t gw, uint32_t wv, const wtz_env_t &V, const wtz_wintask_t *tasks, const wtz_alnitem_t *items, const uint32_t *order, uint32_t lo, uint32_t hi,
 		const wtz_lgap_t *gp, wtz_lres_t *res, uint64_t *wtr, uint32_t *wrm){
 	const wtz_params_t *P = V.P;
@@ -925,7 +928,7 @@ WTZ_HD void wtz_task_gdp(uint32_t gw, uint32_t wv, const wtz_env_t &V, const wtz
 	const uint32_t t = live ? order[idx] : 0u;
 	wtz_lgap_t G; G.slot = 0; G.dq = G.dt = 0; G.w = P->w;
 	if(live) G = gp[t];
-	const int32_t M = P->M, X = P->X, I = P->O, D = P->O, E = P->E;
+	const int32_t M = P->M, X = P->X, I = P->I, D = SP ? P->D : I, E = P->E;
 	wtz_seq_packed q, tt; q.bits = tt.bits = V.R.bits; q.start = tt.start = 0; q.strand = tt.strand = 1; q.comp = tt.comp = 0;
 	if(live){
 		const wtz_alnitem_t &it = items[tasks[t].item];
@@ -977,14 +980,15 @@ WTZ_HD void wtz_task_gtb(uint32_t gw, uint32_t wv, uint32_t RS, const wtz_env_t 
 	g.cigar = rr; g.cigar_len = R.n_runs; g.cells = R.cells;
 	gaps[(it.regs - items[0].regs) + k] = g; done[t] = 1;
 }
+template<bool SP = true>
 WTZ_HD void wtz_task_gdp_all(uint32_t wv, const wtz_lclass_t &L, const wtz_env_t &V, const wtz_wintask_t *tasks, const wtz_alnitem_t *items, const uint32_t *order,
 		const wtz_lgap_t *gp, wtz_lres_t *res, uint64_t *wtr, uint32_t *wrm){
 	uint32_t k = 0; while(k < 3 && wv >= L.wend[k]) k++;
 	const uint32_t wl = wv - (k ? L.wend[k - 1] : 0u);
-	if(k == 0)      wtz_task_gdp<104>(wv, wl, V, tasks, items, order, L.lo[0], L.hi[0], gp, res, wtr, wrm);
-	else if(k == 1) wtz_task_gdp<64>(wv, wl, V, tasks, items, order, L.lo[1], L.hi[1], gp, res, wtr, wrm);
-	else if(k == 2) wtz_task_gdp<32>(wv, wl, V, tasks, items, order, L.lo[2], L.hi[2], gp, res, wtr, wrm);
-	else            wtz_task_gdp<16>(wv, wl, V, tasks, items, order, L.lo[3], L.hi[3], gp, res, wtr, wrm);
+	if(k == 0)      wtz_task_gdp<104, SP>(wv, wl, V, tasks, items, order, L.lo[0], L.hi[0], gp, res, wtr, wrm);
+	else if(k == 1) wtz_task_gdp<64, SP>(wv, wl, V, tasks, items, order, L.lo[1], L.hi[1], gp, res, wtr, wrm);
+	else if(k == 2) wtz_task_gdp<32, SP>(wv, wl, V, tasks, items, order, L.lo[2], L.hi[2], gp, res, wtr, wrm);
+	else            wtz_task_gdp<16, SP>(wv, wl, V, tasks, items, order, L.lo[3], L.hi[3], gp, res, wtr, wrm);
 }
 WTZ_HD void wtz_task_gtb_all(uint32_t wv, const wtz_lclass_t &L, const wtz_env_t &V, const wtz_wintask_t *tasks, const wtz_alnitem_t *items, const uint32_t *order,
 		const wtz_lgap_t *gp, const uint32_t *runoff, uint32_t *runs, const wtz_lres_t *res, wtz_gapres_t *gaps, uint8_t *done, const uint64_t *wtr, const uint32_t *wrm){
@@ -1222,10 +1226,10 @@ WTZ_HD void wtz_task_refine(uint32_t t, const wtz_env_t &V, const wtz_alnitem_t 
 #if defined(__HIP_DEVICE_COMPILE__)
 	int32_t *lds = wtz_wave_scratch();
 	wtz_wave_lds_t L; L.Hs = lds; L.Es = lds + 2048; L.tb = (uint64_t*)(lds + 4096); L.PM = 2047; L.tw = 1032;
-	ok = wtz_refine_wave(pb2.sub(r.x.qb, 1), r.x.qb, pb1.sub(r.x.tb, 1), r.x.tb, P->w, P->M, P->X, P->O, P->O, P->E, r.cigar, r.cigar_len, L, V.pool, out, &y);
+	ok = wtz_refine_wave(pb2.sub(r.x.qb, 1), r.x.qb, pb1.sub(r.x.tb, 1), r.x.tb, P->w, P->M, P->X, P->I, P->D, P->E, r.cigar, r.cigar_len, L, V.pool, out, &y);
 	if(WTZ_LANE != 0) return;
 #else
-	ok = wtz_refine_scalar(pb2.sub(r.x.qb, 1), r.x.qb, pb1.sub(r.x.tb, 1), r.x.tb, P->w, P->M, P->X, P->O, P->O, P->E, r.cigar, r.cigar_len, V.pool, out, &y);
+	ok = wtz_refine_scalar(pb2.sub(r.x.qb, 1), r.x.qb, pb1.sub(r.x.tb, 1), r.x.tb, P->w, P->M, P->X, P->I, P->D, P->E, r.cigar, r.cigar_len, V.pool, out, &y);
 #endif
 	if(!ok || out.bad){ r.bad = 1; res[t] = r; return; }
 	r.x = y; r.cigar = out.a; r.cigar_len = out.n; r.text_len = wtz_cigar_text_len(out.a, out.n);
@@ -1240,7 +1244,7 @@ WTZ_HD void wtz_task_extjob_scalar(uint32_t t, const wtz_env_t &V, wtz_extjob_t 
 	wtz_swmem_t mem; wtz_swmem_init(mem, V.pool);
 	wtz_cigar_t cg; cg.init(V.pool, 64);
 	unsigned long long cells = 0;
-	jb.x = wtz_extend_shift(jb.qlen, jb.q, jb.tlen, jb.t, jb.init_score, jb.W, P->M, P->X, P->O, P->O, P->E, P->T, mem, cg, &cells);
+	jb.x = wtz_extend_shift(jb.qlen, jb.q, jb.tlen, jb.t, jb.init_score, jb.W, P->M, P->X, P->I, P->D, P->E, P->T, mem, cg, &cells);
 	jb.cigar = cg.a; jb.cigar_len = cg.n; jb.bad = (mem.bad || cg.bad); jb.cells = cells;
 }
 

@@ -50,7 +50,7 @@ static __device__ void wtz_task_test_fixed(uint32_t t, const wtz_dpprob_dev_t *p
  * carries the problem, the other lanes are idle (the product packs 64 problems of one shape class into a wave and runs the relative mode) */
 static __device__ void wtz_task_test_lane(uint32_t t, const wtz_dpprob_dev_t *pr, const wtz_params_t *P, wtz_pool_t *pool, wtz_dpres_dev_t *res){
 	const wtz_dpprob_dev_t p = pr[t];
-	const int32_t M = P->M, X = P->X, I = P->O, D = P->O, E = P->E, T = P->T;
+	const int32_t M = P->M, X = P->X, I = P->I, D = P->D, E = P->E, T = P->T;
 	const int32_t init = p.init_score < 0 ? 0 : p.init_score;
 	wtz_dpres_dev_t r; memset(&r, 0, sizeof r);
 	if(p.qlen <= 0 || p.tlen <= 0){ r.x.score = init; r.form = 64; if(WTZ_LANE == 0) res[t] = r; return; }
@@ -80,7 +80,7 @@ static __device__ void wtz_task_test_lane(uint32_t t, const wtz_dpprob_dev_t *pr
 /* form 64 of WTZ_DP_GLOBAL: the lane-per-gap K-sw2 (wtz_lane_global) at the band width the problem names */
 static __device__ void wtz_task_test_lane_global(uint32_t t, const wtz_dpprob_dev_t *pr, const wtz_params_t *P, wtz_pool_t *pool, wtz_dpres_dev_t *res){
 	const wtz_dpprob_dev_t p = pr[t];
-	const int32_t M = P->M, X = P->X, I = P->O, D = P->O, E = P->E;
+	const int32_t M = P->M, X = P->X, I = P->I, D = P->D, E = P->E;
 	wtz_dpres_dev_t r; memset(&r, 0, sizeof r);
 	const int32_t w = p.W, n_col = p.qlen < 2 * w + 1 ? p.qlen : 2 * w + 1;
 	if(p.qlen <= 0 || p.tlen <= 0 || WTZ_ABSDIFF(p.qlen, p.tlen) > w || n_col > WTZ_LN_MAXCOLS || p.tlen > WTZ_LG_MAXROWS){ if(WTZ_LANE == 0) res[t] = r; return; }     /* declined */
@@ -137,8 +137,44 @@ static __device__ void wtz_task_test_global(uint32_t t, const wtz_dpprob_dev_t *
 extern "C" int wtz_test_dp(wtz_ctx_t *c, int32_t kind, int32_t form, const wtz_dp_problem_t *pr, uint32_t n, wtz_dp_result_t *out, uint32_t *cigar, uint64_t cigar_cap){
 	BATCH_ARGS(c, n, pr && out && (cigar || !cigar_cap), NULL, NULL);
 #ifdef WTZ_EMUL
-	(void)kind; (void)form;
-	return wtz_fail(WTZ_E_STATE, "wtz_test_dp drives the DEVICE forms of the banded DPs: it needs the HIP build");
+	/* the host emulation has the scalar bodies only - WTZ_DP_SHIFT 4, WTZ_DP_FIXED / WTZ_DP_GLOBAL 255 -, called as the device's scalar forms call them */
+	if(!((kind == WTZ_DP_SHIFT && form == 4) || ((kind == WTZ_DP_FIXED || kind == WTZ_DP_GLOBAL) && form == 255)))
+		return wtz_fail(WTZ_E_STATE, "wtz_test_dp drives the DEVICE forms of the banded DPs: it needs the HIP build");
+	CTX_ENTER(c);
+	std::vector<uint64_t> h_off; CHK(batch_begin(c, h_off));
+	const wtz_params_t *P = c->dP; wtz_pool_t *pool = c->dpool;
+	uint64_t off = 0;
+	for(uint32_t i = 0; i < n; i++){
+		const wtz_dp_problem_t &p = pr[i];
+		wtz_seq_packed q, t; CHK(dp_problem_views(c, h_off, p, i, true, 0, &q, &t));
+		wtz_swmem_t mem; wtz_swmem_init(mem, pool);
+		wtz_cigar_t cg; cg.init(pool, 64);
+		wtz_aln_t x; memset(&x, 0, sizeof x);
+		unsigned long long cells = 0;
+		if(kind == WTZ_DP_SHIFT) x = wtz_extend_shift(p.q_len, q, p.t_len, t, p.init_score, p.W, P->M, P->X, P->I, P->D, P->E, P->T, mem, cg, &cells);
+		else if(kind == WTZ_DP_FIXED) x = wtz_extend_fixed(p.q_len, q, p.t_len, t, p.init_score, P->w, P->M, P->X, P->I, P->D, P->E, P->T, mem, cg);
+		else {
+			x.score = wtz_global_banded(p.q_len, q, p.t_len, t, P->M, P->X, -P->I, -P->E, -P->D, -P->E, p.W, mem, cg);      /* hzm_aln.h:1407 */
+			int32_t x1 = 0, x2 = 0;
+			for(uint32_t k = 0; k < cg.n; k++){      /* the fold of wtz_task_gap */
+				const int32_t op = (int32_t)(cg.a[k] & 0xF), len = (int32_t)(cg.a[k] >> 4);
+				x.aln += len;
+				if(op == 0){ for(int32_t j = 0; j < len; j++){ if(q.at(x1 + j) == t.at(x2 + j)) x.mat++; else x.mis++; } x1 += len; x2 += len; }
+				else if(op == 1){ x1 += len; x.ins += len; }
+				else { x2 += len; x.del += len; }
+			}
+		}
+		if(mem.bad || cg.bad) return wtz_fail(WTZ_E_POOL, "wtz_test_dp: problem %u ran out of scratch", i);
+		wtz_dp_result_t o; memset(&o, 0, sizeof o);
+		o.score = x.score; o.tb = x.tb; o.te = x.te; o.qb = x.qb; o.qe = x.qe; o.aln = x.aln; o.mat = x.mat; o.mis = x.mis; o.ins = x.ins; o.del = x.del;
+		o.form_used = (uint32_t)form; o.cigar_len = cg.n; o.cigar_off = off; o.cells = cells;
+		if(off + cg.n > cigar_cap) return wtz_fail(WTZ_E_ARG, "wtz_test_dp: CIGAR buffer too small");
+		if(cg.n) memcpy(cigar + off, cg.a, (size_t)cg.n * 4);
+		off += cg.n;
+		out[i] = o;
+		CHK(pool_reset(c));      /* one problem at a time: its scratch goes back */
+	}
+	return WTZ_OK;
 #else
 	CTX_ENTER(c);
 	std::vector<uint64_t> h_off; CHK(batch_begin(c, h_off));
@@ -158,8 +194,8 @@ extern "C" int wtz_test_dp(wtz_ctx_t *c, int32_t kind, int32_t form, const wtz_d
 		if(form == 0){ CHK(run_extjobs(c, V, d_jobs, n)); }
 		else if(form == 3){ WTZ_LAUNCH((wtz_kernel_extjobs<2048, 1032>), n, 64, 0, g_stream, d_jobs, (const uint32_t*)NULL, n, V.P, V.pool, V.pool + 1); }
 		else if(form == 4){ CHK(wtz_launch_wave<K_extjob_scalar>(n, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_extjob_scalar((uint32_t)t, V, d_jobs); })); }
-		else if(form == 5){ WTZ_LAUNCH((wtz_kernel_extjobs_fr<1032>), n, 64, 0, g_stream, d_jobs, (const uint32_t*)NULL, n, V.P, V.pool, V.pool + 1); }
-		else if(form == 7){ WTZ_LAUNCH((wtz_kernel_extjobs_pk<1032>), n, 64, 0, g_stream, d_jobs, (const uint32_t*)NULL, n, V.P, V.pool, V.pool + 1); }      /* frame form, two 16-bit cells per register (round 6) */
+		else if(form == 5){ WTZ_LAUNCH_SP(c, wtz_kernel_extjobs_fr, 1032, n, 64, 0, g_stream, d_jobs, (const uint32_t*)NULL, n, V.P, V.pool, V.pool + 1); }
+		else if(form == 7){ WTZ_LAUNCH_SP(c, wtz_kernel_extjobs_pk, 1032, n, 64, 0, g_stream, d_jobs, (const uint32_t*)NULL, n, V.P, V.pool, V.pool + 1); }      /* frame form, two 16-bit cells per register (round 6) */
 		else return wtz_fail(WTZ_E_ARG, "WTZ_DP_SHIFT: unknown form %d", form);      /* 1, 2 and 6 were kernels that have been removed: their numbers are not reused */
 		CHK(dev_sync());
 		if(form != 0){ c->cnt.ms_ext += tform.stop(); c->cnt.n_extjobs += n; }

@@ -19,7 +19,7 @@ SYMBOLS = [
     "wtz_pairs_windows", "wtz_pairs_align", "wtz_fetch_cigars", "wtz_fetch_cigar_text", "wtz_fetch_cigar_text_begin", "wtz_fetch_cigar_text_end", "wtz_cigar_text_device", "wtz_host_alloc", "wtz_host_free", "wtz_get_counters", "wtz_reset_counters",
     "wtz_test_dp", "wtz_extend_batch", "wtz_local_batch", "wtz_kext_batch", "wtz_align_batch", "wtz_global_batch", "wtz_alignx_batch", "wtz_pwtext_batch", "wtz_pool_info", "wtz_pool_failure_kind",
     "wtz_index_count", "wtz_index_counts_fetch", "wtz_index_finish", "wtz_candidate_groups_begin", "wtz_candidate_groups_end", "wtz_candidate_groups_fetch", "wtz_cand_tail_host", "wtz_zindex_build_subset", "wtz_zindex_build_queries", "wtz_upload_reads_ascii", "wtz_fetch_read_bits", "wtz_append_revcomp_views",
-    "wtz_pairs_seed_region", "wtz_hzmaux_batch", "wtz_set_window_chaining",
+    "wtz_pairs_seed_region", "wtz_hzmaux_batch", "wtz_set_window_chaining", "wtz_set_gap_open",
 ]
 
 
@@ -305,6 +305,12 @@ class Context:
         """wtz_set_window_chaining: 1 (default) = the windows of a scan by their median diagonal, 0 = by chaining_hzmps, as wtmsa and wtcns run align_hzmaux"""
         self.lib.wtz_set_window_chaining.argtypes = [C.c_void_p, C.c_int]
         self._chk(self.lib.wtz_set_window_chaining(self.h, int(fast)))
+
+    def set_gap_open(self, I, D):
+        """wtz_set_gap_open: the opening costs of a run of query-only steps (I) and of target-only steps (D) in every device DP, as the reference takes them
+        (negative or zero; wtmsa: -2, -3); both are params.O until it is called"""
+        self.lib.wtz_set_gap_open.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        self._chk(self.lib.wtz_set_gap_open(self.h, int(I), int(D)))
 
     def zindex_build_subset(self, ids):
         """the z-index of the listed reads only (ascending ids); every other read gets an empty slice"""
