@@ -66,7 +66,7 @@ template<typename TAG, typename F> static int wtz_launch(uint64_t n, F f){
  * thread-per-task grid serialises up to 64 divergent control flows inside every wave; these tasks are chains of
  * dependent memory operations, so what hides their latency is the number of resident waves (up to 32 per CU, 8192 on
  * the chip), not the lanes of one wave.  Stages whose inner loops are regular get wave-cooperative kernels instead
- * (wtz_sw_wave.h). */
+ * (wtz_wave.h and the wtz_sw_*.h files built on it). */
 template<typename TAG, typename F> __global__ void __launch_bounds__(64) wtz_kernel_wave_tasks(uint64_t n, F f){
 	const uint64_t i = blockIdx.x;
 	WTZ_PROF_BEGIN();

@@ -140,7 +140,7 @@ static int run_stitch_fused(wtz_ctx *c, const wtz_env_t &V, const wtz_alnitem_t 
 }
 #endif
 
-/* K-sw3 jobs of a batch: one wavefront per job (wtz_sw_wave.h).  WTZ_SW_SCALAR=1 forces the scalar body,
+/* K-sw3 jobs of a batch: one wavefront per job (wtz_sw_shift.h).  WTZ_SW_SCALAR=1 forces the scalar body,
  * WTZ_SW_CHECK=1 runs both and fails loudly on any difference (on-device cross-check). */
 static int run_extjobs(wtz_ctx *c, const wtz_env_t &V, wtz_extjob_t *d_jobs, uint32_t m, bool leftover = false){
 	if(m == 0) return WTZ_OK;

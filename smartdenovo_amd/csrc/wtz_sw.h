@@ -10,7 +10,7 @@
  * Recurrence (int32, -10000 / -0x40000000 sentinels are part of the semantics):
  *   m = H(i-1,j-1)+S;  H = max{m,E,F} (ties m>E>F);  E' = max{E+e, m+I+e};  F' = max{F+e, m+D+e}
  * one trace byte per cell: bits0-1 H source, bit2 E extended, bit5 F extended.
- * The wave-parallel kernels in wtz_sw_wave.h compute the same cells row by row with lanes
+ * The wave-parallel kernels in wtz_sw_shift.h / wtz_sw_fixed.h / wtz_sw_global.h compute the same cells row by row with lanes
  * across the band and a max-plus prefix scan for F; these scalar bodies are their on-device
  * cross-check and the form used for the many tiny K-sw1/K-sw2 problems.
  */

@@ -22,7 +22,7 @@
  *   - the row maximum: lanes entirely beyond the band end are masked after their local reduction; the one lane the band end cuts
  *     through checks whether its local arg-max fell on a cell beyond it and only then (rare: that cell is W columns off the running
  *     maximum) the wave repeats the reduction with per-cell masks.
- * Trace layout (this file owns it, both frame forms write it; wtz_shift_traceback in wtz_sw_wave.h walks it and describes the cell):
+ * Trace layout (this file owns it, both frame forms write it; wtz_shift_traceback in wtz_sw_shift.h walks it and describes the cell):
  * rows are carved from the transient pool 64 at a time (chunk table tr.chunk, one pointer per 64 rows); a row is zrow = CQ * 256 bytes (CQ = the form's
  * trace dwords per lane: ceil(C/4) here, ceil(C2/4) in wtz_sw_frame16.h) in the lane-transposed order (row, q, lane), so that each of the CQ stores of a row writes 256 contiguous bytes;
  * byte k of lane l belongs to band-relative column l*C + k; only lanes that own band cells store, what lies right of the band end is never read by the walk.
@@ -37,7 +37,7 @@
 #ifndef WTZ_SW_FRAME_H
 #define WTZ_SW_FRAME_H
 
-#include "wtz_sw_wave.h"
+#include "wtz_sw_shift.h"
 
 #ifdef __HIPCC__
 

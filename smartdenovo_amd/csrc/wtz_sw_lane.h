@@ -38,7 +38,7 @@
 #define WTZ_SW_LANE_H
 
 #include "wtz_sw.h"
-#include "wtz_sw_wave.h"
+#include "wtz_wave.h"
 
 #define WTZ_LN_MAXCOLS 104          /* band columns of the widest class: 2 * 51 + 1 >= n_col of the default -w 50 */
 #define WTZ_LN_MAXROWS 511          /* rows of a problem (9 bits of the sort key) */

@@ -11,7 +11,10 @@
 #define WTZ_TASKS_H
 
 #include "wtz_sw.h"
-#include "wtz_sw_wave.h"
+#include "wtz_sw_shift.h"
+#include "wtz_sw_fixed.h"
+#include "wtz_sw_global.h"
+#include "wtz_sw_refine.h"
 #include "wtz_sw_lane.h"
 #include "wtz_dotmatrix.h"
 

@@ -85,3 +85,86 @@ def test_oracle_equals_reference_vectors(kind, vec, ora):
         assert (cg[:m] == vec.expected_cigar(i)).all() and m == vec.expected_cigar(i).size, "problem %d (%s): CIGAR" % (i, vec.cls[i])
         n += 1
     assert n > 40
+
+
+def _ext_geometry(qlen, tlen, init, W, S):
+    """wtz_ext_geometry (wtz_sw.h) with one opening cost: (w, ql, tl, n_col)"""
+    w = W
+    if w > 0:
+        w = min(w, max(int((min(qlen, tlen) * S["M"] + init - S["T"] + S["O"]) / -S["E"]) + 1, 1))
+    else:
+        w = -w
+    w = min(w, max(qlen, tlen))
+    if qlen < tlen:
+        ql, tl = qlen, (qlen + w if qlen + w < tlen else tlen)
+    else:
+        tl, ql = tlen, (tlen + w if tlen + w < qlen else qlen)
+    return w, ql, tl, min(tl, 2 * w + 1)
+
+
+def test_vectors_reach_the_paths_of_the_register_forms(vec):
+    """The K-sw1 and K-sw2 register forms (wtz_sw_fixed.h, wtz_sw_global.h) have paths a short problem never enters; the vectors hold a problem for each, told
+    from the lengths, the recorded answers and the recorded CIGARs alone (the forms are the choices of wtz_fixed_problem_wave / wtz_gap_problem_wave; LDS slices of
+    12 288 bytes, 1 024 of them sequence words):
+      K-sw1, trace in LDS, last computed row even (its nibbles are written by the flush behind the row loop) and odd;
+      K-sw1, trace in the pool, a walk of more than one staged block (more than 2 RB rows at the problem's zrow), last computed row even and odd;
+      K-sw2, trace in LDS, tlen odd (last row even: the flush) and even;
+      K-sw2, trace in the pool, tlen > 2048 and a walk that crosses row 2 048 with columns left (the walk reloads the target words there).
+    The last computed row of a K-sw1 problem is known where the answer ends on the last query row and the geometry does not cut the rows: ql - 1."""
+    S = vec.meta["scores"]
+    ztr_bytes = 12288 - 1024
+    seen = set()
+    for i in np.nonzero(vec.kind == 1)[0]:
+        qlen, tlen, init = int(vec.qlen[i]), int(vec.tlen[i]), max(int(vec.init[i]), 0)
+        if qlen <= 0 or tlen <= 0:
+            continue
+        w, ql, tl, n_col = _ext_geometry(qlen, tlen, init, int(vec.w_param[i]), S)
+        if not (int(vec.aln[i][4]) == qlen and ql == qlen):      # qe == qlen: the rows ran to the end
+            continue
+        run_bytes, zrow, hmax = 4 * (ql + tl + 4), (n_col + 3) & ~3, init + S["M"] * min(ql, tl)
+        shape = ql <= 2048 and (tl + 63) // 32 + 1 <= 128
+        lds = shape and n_col <= 128 and hmax < (1 << 23) and ((ql + 1) // 2) * zrow + run_bytes <= ztr_bytes
+        pool = shape and not lds and n_col <= 512 and hmax < ((1 << 23) if n_col <= 128 else (1 << 21)) and 4096 + run_bytes <= ztr_bytes
+        rb = 32 if zrow <= 128 else (16 if zrow <= 256 else 8)
+        # the walk starts on (qe - 1, te - 1) and steps while both coordinates are inside (what is left then is appended as one gap, not walked): replay the recorded
+        # CIGAR backwards, op 0 moves both, 1 (I) a row, 2 (D) a column; rows walked = the rows between the start and the cell the walk stops on
+        r, c = int(vec.aln[i][4]) - 1, int(vec.aln[i][2]) - 1
+        r0 = r
+        for cw in vec.expected_cigar(i)[::-1]:
+            op, ln = int(cw) & 0xF, int(cw) >> 4
+            for _ in range(ln):
+                if r < 0 or c < 0:
+                    break
+                r -= op != 2
+                c -= op != 1
+        rows_walked = r0 - max(r, -1)
+        if lds:
+            seen.add(("f_lds", (ql - 1) & 1))
+        if pool and rows_walked > 2 * rb:
+            seen.add(("f_pool_blocks", (ql - 1) & 1))
+    for i in np.nonzero(vec.kind == 2)[0]:
+        dq, dt, w = int(vec.qlen[i]), int(vec.tlen[i]), int(vec.W[i])
+        if dq <= 0 or dt <= 0:
+            continue
+        n_col = min(dq, 2 * w + 1)
+        zrow, run_bytes, qwords = (n_col + 3) & ~3, 4 * (dq + dt + 4), (dq + 63) // 32 + 1
+        qbytes = (qwords * 8 + 15) & ~15
+        lds = n_col <= 128 and dt <= 2048 and qwords <= 128 and ((dt + 1) // 2) * zrow + run_bytes <= ztr_bytes
+        pool = not lds and n_col <= 512 and qbytes + 4096 <= 12288
+        if lds:
+            seen.add(("g_lds", dt & 1))
+        if pool and dt > 2048:
+            # rows run over the target: walk the recorded CIGAR backwards from (dt - 1, dq - 1); op 0 moves both, 2 (D) a row, 1 (I) a column
+            ii, k = dt - 1, dq - 1
+            for c in vec.expected_cigar(i)[::-1]:
+                op, ln = int(c) & 0xF, int(c) >> 4
+                for _ in range(ln):
+                    if ii < 2048:
+                        break
+                    ii -= op != 1
+                    k -= op != 2
+                if ii < 2048:
+                    break
+            if ii == 2047 and k >= 0:
+                seen.add(("g_pool_reload", 0))
+    assert seen >= {("f_lds", 0), ("f_lds", 1), ("f_pool_blocks", 0), ("f_pool_blocks", 1), ("g_lds", 0), ("g_lds", 1), ("g_pool_reload", 0)}, sorted(seen)
