@@ -267,7 +267,19 @@ void  wtz_host_free(void *p);
  *        WTZ_DP_SHIFT : 3 LDS-ring kernel (+ its scalar fallback), 4 scalar body, 5 one-wave kernel in the anti-diagonal frame, 7 the same with two 16-bit cells
  *                       per register; 1, 2 and 6 were kernels that have been removed: their numbers are not reused, the call returns WTZ_E_ARG
  *        WTZ_DP_FIXED / WTZ_DP_GLOBAL : C | 16*pool  (C = 1, 2, 4, 8 band columns per lane; +16 = 4-bit trace in the pool instead of LDS),
- *                       255 scalar body; WTZ_DP_GLOBAL also 32 = LDS-ring wave DP, 33 = the same with the 72 KB slice of the wide launch
+ *                       255 scalar body; WTZ_DP_GLOBAL also 32 = LDS-ring wave DP, 33 = the same with the 72 KB slice of the wide launch;
+ *                       64 = the lane bodies (one lane per problem, wtz_sw_lane.h) with lane 0 alone in its wavefront: K-sw1 in the ABSOLUTE mode (the reference's
+ *                       function for the init_score given; declined beyond 104 band columns, 511 rows, 1500 rows + columns or init_score 2^20), K-sw2 at the band
+ *                       width W the problem names (declined for |q_len - t_len| > W, beyond 104 band columns or 768 rows, or an empty side);
+ *                       65 = the lane bodies the way the product runs them: problems 64k .. 64k+63 of the call share wavefront k IN THE CALLER'S ORDER (nothing is
+ *                       sorted, the last wavefront may be partial; a declined problem leaves its lane idle), the instantiation of a wavefront is the class (16 / 32 /
+ *                       64 / 104 band columns) of its widest live problem, and the DP and the traceback are two launches around a lane-interleaved trace block in
+ *                       the transient pool (K_ldp / K_ltb, K_gdp / K_gtb).  K-sw1 runs in the RELATIVE mode (init_score 0); the answer is max(init_score, 0) + the
+ *                       relative score, unless the fold's rule (wtz_lres_declined) says the shift is not the reference's: then, and for what the planner leaves to
+ *                       the chained kernel (a band that depends on init_score, the envelope of form 64, an empty side), form_used = 0.  For form 65 only, W > 0 of
+ *                       a WTZ_DP_FIXED problem is the -w of that problem in the place of params.w (one call can hold waves at several -w); K-sw2 as form 64, the
+ *                       lanes of a wavefront at their own W, the score reported whether or not the caller would double the band.  The host emulation
+ *                       (tests/emul) answers form 65 with the same bodies, one problem per "wavefront"
  *   out[i].form_used = the form that produced the result, 0 = the forced form does not cover this problem (result untouched). */
 #define WTZ_DP_SHIFT  0
 #define WTZ_DP_FIXED  1

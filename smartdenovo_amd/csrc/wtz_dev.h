@@ -92,6 +92,9 @@ template<> struct wtz_occ<K_gdp> { static constexpr int waves = WTZ_OCC_LDP; };
 /* their tracebacks: chains of dependent loads, nothing to keep in registers */
 template<> struct wtz_occ<K_ltb> { static constexpr int waves = 8; };
 template<> struct wtz_occ<K_gtb> { static constexpr int waves = 8; };
+/* form 65 of wtz_test_dp runs the same lane bodies in the same two launches: the same register budgets */
+template<> struct wtz_occ<K_test_ldp> { static constexpr int waves = WTZ_OCC_LDP; };
+template<> struct wtz_occ<K_test_ltb> { static constexpr int waves = 8; };
 template<typename TAG, typename F> __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(wtz_occ<TAG>::waves, 8))) wtz_kernel_coop_tasks(uint64_t n, F f){
 	const uint64_t i = blockIdx.x;
 	WTZ_PROF_BEGIN();

@@ -89,6 +89,8 @@ struct K_extcopy;
 struct K_globcopy;
 struct K_glob_ring;
 struct K_glob_scalar;
+struct K_test_ldp;      /* form 65 of wtz_test_dp (wtz_testdp.h): the two launches of a lane pipeline, at K_ldp's / K_ltb's occupancy (wtz_dev.h) */
+struct K_test_ltb;
 
 #include "wtz_dev.h"
 #include "wtz_ctx.h"

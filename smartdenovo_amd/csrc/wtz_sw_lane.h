@@ -76,6 +76,10 @@ typedef struct {
 	int32_t minrow;               /* REL: smallest row maximum (relative) */
 	uint32_t n_runs, flags, cells;
 } wtz_lres_t;
+/* The fold's rule: with a = max(init_score, 0) now known, would one of the absolute tests the relative mode left open have gone the other way?  A row maximum
+ * at or below 0 (kswx.h:280, 302), or an end candidate that was taken although it is not above 0 (kswx.h:304).  true: the shifted answer is not the reference's,
+ * the problem belongs to the chained kernel.  Called by wtz_task_lfold and by form 65 of wtz_test_dp. */
+WTZ_HD bool wtz_lres_declined(int32_t a, const wtz_lres_t &r){ return a + r.minrow <= 0 || ((r.flags & WTZ_LR_USEDG) && a + r.score <= 0); }
 
 template<int NC> struct wtz_lane_geo {
 	static constexpr int KW = (NC + 15) / 16;                                    /* 32-bit words of the target window */

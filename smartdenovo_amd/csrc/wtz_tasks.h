@@ -639,7 +639,7 @@ WTZ_HD void wtz_task_lfold(uint32_t t, const wtz_env_t &V, const wtz_wintask_t *
 			if(pr.qlen > 0 && pr.tlen > 0){
 				const wtz_lres_t r = RES[j];
 				if(!(r.flags & WTZ_LR_DONE)){ bad = 1; stop = true; break; }
-				if(a + r.minrow <= 0 || ((r.flags & WTZ_LR_USEDG) && a + r.score <= 0)){ const uint32_t z = WTZ_ATOMIC_INC32(&fblist[0]); fblist[1 + z] = t; return; }
+				if(wtz_lres_declined(a, r)){ const uint32_t z = WTZ_ATOMIC_INC32(&fblist[0]); fblist[1 + z] = t; return; }
 				x.score = a + r.score;
 				x.aln += r.mat + r.mis + r.ins + r.del; x.mat += r.mat; x.mis += r.mis; x.ins += r.ins; x.del += r.del;
 				x.te += r.te; x.qe += r.qe;

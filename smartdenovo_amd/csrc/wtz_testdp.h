@@ -16,6 +16,88 @@ struct K_test_lane;
 typedef struct { wtz_seq_packed q, t; int32_t qlen, tlen, init_score, W; } wtz_dpprob_dev_t;
 typedef struct { wtz_aln_t x; uint32_t *cigar; uint32_t cigar_len; int32_t form, bad; unsigned long long cells; } wtz_dpres_dev_t;
 
+/*
+ * Form 65: the lane bodies of wtz_sw_lane.h the way the product runs them - WTZ_NLANES problems per wavefront in the CALLER's order (problems 64k .. 64k+63 share
+ * wavefront k; nothing is sorted, the last wavefront may be partial), K-sw1 in the relative mode, and two launches: the forward DP writes the wave's lane-interleaved
+ * trace block into the transient pool (K_ldp / K_gdp), the second launch walks it back, lane l the rows lane l wrote (K_ltb / K_gtb).  The instantiation NC of a
+ * wavefront is the class of its widest live problem.  The task bodies below restate the wrappers wtz_task_ldp / _ltb / _gdp / _gtb around the SAME lane bodies, with
+ * a test problem in the place of a window's slot; the host emulation runs them with one lane, one problem per "wavefront".
+ */
+WTZ_HD int32_t wtz_test_l65_band(const wtz_dpprob_dev_t &p, const wtz_params_t *P){ return p.W > 0 ? p.W : P->w; }      /* WTZ_DP_FIXED: W > 0 names the -w of this problem, 0 = params.w */
+/* what wtz_task_lplan leaves to the chained kernel (and an empty side): false = form 65 declines the problem */
+WTZ_HD bool wtz_test_l65_fixed_geo(const wtz_dpprob_dev_t &p, const wtz_params_t *P, int32_t &W, int32_t &ql, int32_t &tl, int32_t &n_col){
+	W = wtz_test_l65_band(p, P); ql = tl = n_col = 0;
+	if(p.qlen <= 0 || p.tlen <= 0) return false;
+	int32_t W1 = W, ql1, tl1, nc1;
+	wtz_ext_geometry(p.qlen, p.tlen, 0, W, P->M, P->I, P->D, P->E, P->T, ql, tl, n_col);
+	wtz_ext_geometry(p.qlen, p.tlen, 1 << 24, W1, P->M, P->I, P->D, P->E, P->T, ql1, tl1, nc1);
+	return !(W != W1 || n_col > WTZ_LN_MAXCOLS || ql > WTZ_LN_MAXROWS || ql + tl > WTZ_LN_MAXSPAN);
+}
+/* form 64's envelope of the lane K-sw2 */
+WTZ_HD bool wtz_test_l65_global_geo(const wtz_dpprob_dev_t &p, int32_t &n_col){
+	n_col = p.qlen < 2 * p.W + 1 ? p.qlen : 2 * p.W + 1;
+	return !(p.qlen <= 0 || p.tlen <= 0 || p.W <= 0 || WTZ_ABSDIFF(p.qlen, p.tlen) > p.W || n_col > WTZ_LN_MAXCOLS || p.tlen > WTZ_LG_MAXROWS);
+}
+/* first launch, wavefront wv: wtr[wv] = the wave's trace block, wrs[wv] = its trace dwords per row; res[i].flags stays 0 for a problem that was declined */
+template<bool GLOBAL>
+WTZ_HD void wtz_task_test_ldp(uint32_t wv, const wtz_dpprob_dev_t *pr, uint32_t n, const wtz_env_t &V, wtz_lres_t *res, uint64_t *wtr, uint32_t *wrs){
+	const wtz_params_t *P = V.P;
+	const uint32_t idx = wv * WTZ_NLANES + WTZ_LANE;
+	wtz_dpprob_dev_t p; memset(&p, 0, sizeof p);
+	p.q.bits = p.t.bits = V.R.bits; p.q.strand = p.t.strand = 1;
+	bool live = idx < n;
+	if(live) p = pr[idx];
+	const int32_t M = P->M, X = P->X, I = P->I, D = P->D, E = P->E, T = P->T;
+	int32_t W = P->w, ql = 0, tl = 0, n_col = 0;
+	if(live) live = GLOBAL ? wtz_test_l65_global_geo(p, n_col) : wtz_test_l65_fixed_geo(p, P, W, ql, tl, n_col);
+	if(!live){ ql = tl = n_col = 0; p.qlen = p.tlen = 0; }
+	const int32_t rows = GLOBAL ? p.tlen : ql;
+	const int32_t ncmax = wtz_lane_wmax(n_col);
+	const uint32_t RS = wtz_lane_rs(ncmax);
+	const uint32_t rows_max = (uint32_t)wtz_lane_wmax(rows);
+	uint64_t pa = 0;
+	if(WTZ_LANE == 0){
+		pa = (uint64_t)(uintptr_t)wtz_pool_alloc(V.pool + 1, (size_t)WTZ_NLANES * rows_max * RS * 4 + 16);      /* as wtz_task_ldp / wtz_task_gdp: the transient pool */
+		wtr[wv] = pa; wrs[wv] = RS;
+	}
+	pa = wtz_coop_bcast64(pa);
+	if(pa == 0) return;                       /* the host reports the pool */
+	uint32_t *tr = (uint32_t*)(uintptr_t)pa;
+	wtz_lres_t R; memset(&R, 0, sizeof R);
+	if(GLOBAL){
+		if(ncmax <= 16)      wtz_lane_global<16>(live, p.qlen, p.q, p.tlen, p.t, p.W, M, X, -I, -E, -D, -E, tr, R);
+		else if(ncmax <= 32) wtz_lane_global<32>(live, p.qlen, p.q, p.tlen, p.t, p.W, M, X, -I, -E, -D, -E, tr, R);
+		else if(ncmax <= 64) wtz_lane_global<64>(live, p.qlen, p.q, p.tlen, p.t, p.W, M, X, -I, -E, -D, -E, tr, R);
+		else                 wtz_lane_global<104>(live, p.qlen, p.q, p.tlen, p.t, p.W, M, X, -I, -E, -D, -E, tr, R);
+	} else {
+		if(ncmax <= 16)      wtz_lane_fixed<16, false>(live, p.qlen, p.q, p.tlen, p.t, 0, W, ql, tl, M, X, I, D, E, T, tr, R);
+		else if(ncmax <= 32) wtz_lane_fixed<32, false>(live, p.qlen, p.q, p.tlen, p.t, 0, W, ql, tl, M, X, I, D, E, T, tr, R);
+		else if(ncmax <= 64) wtz_lane_fixed<64, false>(live, p.qlen, p.q, p.tlen, p.t, 0, W, ql, tl, M, X, I, D, E, T, tr, R);
+		else                 wtz_lane_fixed<104, false>(live, p.qlen, p.q, p.tlen, p.t, 0, W, ql, tl, M, X, I, D, E, T, tr, R);
+	}
+	if(live) res[idx] = R;
+}
+/* second launch: lane l walks the rows lane l wrote; the runs stay in traceback order (the host reverses them) */
+template<bool GLOBAL>
+WTZ_HD void wtz_task_test_ltb(uint32_t wv, const wtz_dpprob_dev_t *pr, uint32_t n, const wtz_env_t &V, const uint64_t *runoff, uint32_t *runs, wtz_lres_t *res, const uint64_t *wtr, const uint32_t *wrs){
+	const uint32_t idx = wv * WTZ_NLANES + WTZ_LANE;
+	const uint64_t pa = wtr[wv];
+	if(idx >= n || pa == 0) return;
+	wtz_lres_t R = res[idx];
+	if(!(R.flags & WTZ_LR_DONE)) return;
+	const wtz_dpprob_dev_t p = pr[idx];
+	const uint32_t *tr = (const uint32_t*)(uintptr_t)pa;      /* lane-interleaved, as the first launch wrote it */
+	if(GLOBAL){
+		const int32_t r0 = p.tlen - 1, c0 = (r0 + p.W + 1 < p.qlen ? r0 + p.W + 1 : p.qlen) - 1;
+		wtz_lane_traceback<true>(true, r0, c0, p.W, wrs[wv], p.t, p.tlen, p.q, p.qlen, tr, runs + runoff[idx], R);
+	} else {
+		int32_t W, ql, tl, n_col;
+		(void)wtz_test_l65_fixed_geo(p, V.P, W, ql, tl, n_col);
+		wtz_lane_traceback<false>(true, R.qe - 1, R.te - 1, W, wrs[wv], p.q, p.qlen, p.t, p.tlen, tr, runs + runoff[idx], R);
+	}
+	res[idx] = R;
+}
+
 #ifndef WTZ_EMUL
 static __device__ void wtz_testdp_store(wtz_dpres_dev_t *res, const wtz_aln_t &x, bool from_runs, const uint32_t *runs, uint32_t n_runs, const wtz_cigar_t &tmp,
 		wtz_pool_t *pool, int form, int bad, unsigned long long cells){
@@ -134,10 +216,64 @@ static __device__ void wtz_task_test_global(uint32_t t, const wtz_dpprob_dev_t *
 }
 #endif
 
+/* form 65 of WTZ_DP_FIXED / WTZ_DP_GLOBAL, both back ends: the two launches, then the fold's rule per K-sw1 problem */
+static int test_dp_lanes(wtz_ctx_t *c, int32_t kind, const wtz_dp_problem_t *pr, uint32_t n, wtz_dp_result_t *out, uint32_t *cigar, uint64_t cigar_cap){
+	CTX_ENTER(c);
+	std::vector<uint64_t> h_off; CHK(batch_begin(c, h_off));
+	std::vector<wtz_dpprob_dev_t> hp(n);
+	std::vector<uint64_t> h_ro((size_t)n + 1, 0);      /* room for the runs of problem i: at most one per row and column, as the planners size it */
+	for(uint32_t i = 0; i < n; i++){
+		const wtz_dp_problem_t &p = pr[i];
+		wtz_dpprob_dev_t d; CHK(dp_problem_views(c, h_off, p, i, true, 0, &d.q, &d.t)); d.qlen = p.q_len; d.tlen = p.t_len; d.init_score = p.init_score; d.W = p.W;
+		hp[i] = d; h_ro[i + 1] = h_ro[i] + (uint64_t)(p.q_len > 0 ? p.q_len : 0) + (uint64_t)(p.t_len > 0 ? p.t_len : 0) + 4u;
+	}
+	const wtz_env_t V = ctx_env(c);
+	const uint32_t nw = (uint32_t)(((uint64_t)n + WTZ_NLANES - 1) / WTZ_NLANES);
+	wtz_dpprob_dev_t *d_pr = NULL; wtz_lres_t *d_res = NULL; uint64_t *d_ro = NULL, *d_wtr = NULL; uint32_t *d_runs = NULL, *d_wrs = NULL;
+	CHK(batch_upload(hp, std::vector<uint32_t>(), &d_pr, (uint32_t**)NULL, &d_res));
+	CHK(dev_alloc((void**)&d_ro, ((size_t)n + 1) * 8)); CHK(dev_h2d(d_ro, h_ro.data(), ((size_t)n + 1) * 8));
+	CHK(dev_alloc((void**)&d_runs, (size_t)h_ro[n] * 4));
+	CHK(dev_alloc((void**)&d_wtr, (size_t)nw * 8)); CHK(dev_set(d_wtr, 0, (size_t)nw * 8));
+	CHK(dev_alloc((void**)&d_wrs, (size_t)nw * 4)); CHK(dev_set(d_wrs, 0, (size_t)nw * 4));
+	if(kind == WTZ_DP_FIXED){
+		CHK(wtz_launch_coop<K_test_ldp>(nw, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_test_ldp<false>((uint32_t)t, d_pr, n, V, d_res, d_wtr, d_wrs); }, 0));
+		CHK(wtz_launch_coop<K_test_ltb>(nw, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_test_ltb<false>((uint32_t)t, d_pr, n, V, d_ro, d_runs, d_res, d_wtr, d_wrs); }, 0));
+	} else {
+		CHK(wtz_launch_coop<K_test_ldp>(nw, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_test_ldp<true>((uint32_t)t, d_pr, n, V, d_res, d_wtr, d_wrs); }, 0));
+		CHK(wtz_launch_coop<K_test_ltb>(nw, [=] WTZ_LAMBDA (uint64_t t){ wtz_task_test_ltb<true>((uint32_t)t, d_pr, n, V, d_ro, d_runs, d_res, d_wtr, d_wrs); }, 0));
+	}
+	CHK(dev_sync());
+	CHK(tpool_check(c, "wtz_test_dp"));
+	CHK(pool_check(c, "wtz_test_dp"));
+	std::vector<wtz_lres_t> hr(n); std::vector<uint32_t> h_runs((size_t)h_ro[n]);
+	CHK(dev_d2h(hr.data(), d_res, (size_t)n * sizeof(wtz_lres_t)));
+	CHK(dev_d2h(h_runs.data(), d_runs, (size_t)h_ro[n] * 4));
+	uint64_t off = 0;
+	for(uint32_t i = 0; i < n; i++){
+		const wtz_lres_t &r = hr[i];
+		wtz_dp_result_t o; memset(&o, 0, sizeof o);
+		const int32_t a = pr[i].init_score < 0 ? 0 : pr[i].init_score;                 /* kswx.h:241 */
+		const bool answered = (r.flags & WTZ_LR_DONE) && (kind == WTZ_DP_GLOBAL || !wtz_lres_declined(a, r));
+		if(answered){
+			if(r.n_runs > h_ro[i + 1] - h_ro[i]) return wtz_fail(WTZ_E_STATE, "wtz_test_dp: problem %u wrote %u runs into room for %llu", i, r.n_runs, (unsigned long long)(h_ro[i + 1] - h_ro[i]));
+			o.score = kind == WTZ_DP_GLOBAL ? r.score : a + r.score;
+			if(kind == WTZ_DP_FIXED){ o.qe = r.qe; o.te = r.te; }
+			o.mat = r.mat; o.mis = r.mis; o.ins = r.ins; o.del = r.del; o.aln = r.mat + r.mis + r.ins + r.del;
+			o.form_used = 65; o.cigar_len = r.n_runs; o.cigar_off = off; o.cells = r.cells;
+			if(off + r.n_runs > cigar_cap) return wtz_fail(WTZ_E_ARG, "wtz_test_dp: CIGAR buffer too small");
+			for(uint32_t k = 0; k < r.n_runs; k++) cigar[off + k] = h_runs[(size_t)h_ro[i] + r.n_runs - 1 - k];      /* traceback order -> CIGAR order */
+			off += r.n_runs;
+		}
+		out[i] = o;
+	}
+	return WTZ_OK;
+}
+
 extern "C" int wtz_test_dp(wtz_ctx_t *c, int32_t kind, int32_t form, const wtz_dp_problem_t *pr, uint32_t n, wtz_dp_result_t *out, uint32_t *cigar, uint64_t cigar_cap){
 	BATCH_ARGS(c, n, pr && out && (cigar || !cigar_cap), NULL, NULL);
+	if((kind == WTZ_DP_FIXED || kind == WTZ_DP_GLOBAL) && form == 65) return test_dp_lanes(c, kind, pr, n, out, cigar, cigar_cap);
 #ifdef WTZ_EMUL
-	/* the host emulation has the scalar bodies only - WTZ_DP_SHIFT 4, WTZ_DP_FIXED / WTZ_DP_GLOBAL 255 -, called as the device's scalar forms call them */
+	/* beside form 65 (above) the host emulation has the scalar bodies only -WTZ_DP_SHIFT 4, WTZ_DP_FIXED / WTZ_DP_GLOBAL 255 -, called as the device's scalar forms call them */
 	if(!((kind == WTZ_DP_SHIFT && form == 4) || ((kind == WTZ_DP_FIXED || kind == WTZ_DP_GLOBAL) && form == 255)))
 		return wtz_fail(WTZ_E_STATE, "wtz_test_dp drives the DEVICE forms of the banded DPs: it needs the HIP build");
 	CTX_ENTER(c);
